@@ -5,15 +5,20 @@ configuration: N = 2^16, Goldilocks prime 2^64-2^32+1, batch 4096 per GPU.
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N --single-process ...      one process, N devices through ntt_plan_clone (SURVEY 8e's other form)
+  ... --full                  everything below the headline figure as well (verification, roofline, CPU baseline, inverse, configs)
+  ... --dump-outputs DIR      a seeded sample of the last timed step's output as DIR/*.npy (dump_outputs)
 
 One step = one forward transform of the whole resident batch (input buffer -> output
 buffer, both already in HBM).  Weak scaling: every rank owns `batch` polynomials and never
 talks to the others in the timed region; the only collective is the one-off twiddle-table
 broadcast from rank 0 (RCCL).  Rank 0 prints ONE JSON line.
 
-No time without a check (the reference prints its launch times and then compares every word, src/test.cpp:203-247):
-after the timed region EVERY rank (every device in --single-process) inverts its own output and compares it with its own
-input, and checks out[b][0] == sum(a[b][:]) mod p on sampled rows (an oracle-free invariant of the network); the verdicts
+A plain run sets up, warms up, times --steps steps, writes the outputs when asked and prints the line's headline keys; all
+that follows is --full's.
+
+With --full no time goes without a check (the reference prints its launch times and then compares every word,
+src/test.cpp:203-247): after the timed region EVERY rank (every device in --single-process) inverts its own output and compares it
+with its own input, and checks out[b][0] == sum(a[b][:]) mod p on sampled rows (an oracle-free invariant of the network); the verdicts
 are reduced with all_reduce(MIN), every rank's device identity and step time are gathered into the line, and the process
 exits non-zero when any rank failed.
 
@@ -669,6 +674,44 @@ def base_line(args, logn, batch, world, value, elapsed, passes, table_broadcast,
 
 PREWARM = 8  # untimed, before the W warm-up steps: first touches of 4 GiB (TLB) and the clock ramp
 
+# --dump-outputs: a fixed, seeded sample of the last timed step's output, below 64 MB in all whatever the shape
+DUMP_SEED = 0x5EED
+DUMP_SAMPLE_BYTES = 32 * 10**6  # the sampled rows' two float64 halves
+DUMP_WORD0_ROWS = 1 << 19       # word 0 (the coefficient sum) of at most this many rows
+
+
+def dump_outputs(directory, y):
+    """Write what the timed path returned in its last step, y = forward(x) ([batch][N] u64 words in an int64 tensor), to
+    directory/<name>.npy as float64 that holds every bit: each word split into its low and high 32-bit halves.
+      forward_out_rows_lo / _hi    [R][C]: the rows forward_out_rows (a seeded sample, every row when they fit) at the columns
+                                   forward_out_cols (every column unless one row alone exceeds the sample budget)
+      forward_out_word0_lo / _hi   word 0 of the first min(batch, DUMP_WORD0_ROWS) rows: one word of every row
+    The sample depends on the shape alone, so two runs with the same arguments write the same positions."""
+    import numpy as np
+    import torch
+
+    batch, n = y.shape
+    rng = np.random.default_rng(DUMP_SEED)
+    cols = np.arange(n) if n * 16 <= DUMP_SAMPLE_BYTES else np.sort(rng.choice(n, DUMP_SAMPLE_BYTES // 16, replace=False))
+    nrows = min(batch, DUMP_SAMPLE_BYTES // (16 * len(cols)))
+    rows = np.arange(batch) if nrows == batch else np.sort(rng.choice(batch, nrows, replace=False))
+    sample = y.index_select(0, torch.from_numpy(rows).to(y.device))
+    if len(cols) < n:
+        sample = sample.index_select(1, torch.from_numpy(cols).to(y.device))
+    word0 = y[: min(batch, DUMP_WORD0_ROWS), 0]
+
+    def halves(t):
+        w = t.cpu().numpy().view(np.uint64)
+        return (w & np.uint64(0xFFFFFFFF)).astype(np.float64), (w >> np.uint64(32)).astype(np.float64)
+
+    arrays = {"forward_out_rows": rows.astype(np.float64), "forward_out_cols": cols.astype(np.float64)}
+    arrays["forward_out_rows_lo"], arrays["forward_out_rows_hi"] = halves(sample)
+    arrays["forward_out_word0_lo"], arrays["forward_out_word0_hi"] = halves(word0)
+    assert sum(a.nbytes for a in arrays.values()) < 64 * 10**6
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
 
 def rank0_extras(torch, args, plan, table, x, y, stream, passes, out, world):
     """Rank 0 / device 0 only, AFTER the timed region and the verification: step-time distribution, the roofline object
@@ -1133,17 +1176,22 @@ def run_single_process(args):
                     "ntt_plan_clone: tables copied device-to-device (hipMemcpyPeer)" if ndev > 1 else "none (one device)",
                     "single-process")
     out["value_by_device_events"] = batch * ndev / (max(dev_ms) * 1e-3)
-    # every device proves its shard, exactly as every rank does in the process-per-GPU form
-    recs, flags = [], [True, True]
-    for i, (d, pl, x, y, st) in enumerate(zip(devs, plans, xs, ys, streams)):
-        with torch.cuda.device(d):
-            v = verify_shard(torch, pl, x, y, p, st)
-        flags = [flags[0] and v["round_trip_identical"], flags[1] and v["coefficient_sum_invariant"]]
-        recs.append(dict(device_identity(torch, d), rank=i, ms_per_step=dev_ms[i], **v))
-    fields, code = verdict_fields(flags, recs, ndev, one_device_ok=rehearsal)
-    out.update(fields)
-    with torch.cuda.device(devs[0]), torch.cuda.stream(streams[0]):  # torch's own kernels (the device copy) on the launch stream too
-        code = max(code, rank0_extras(torch, args, plan0, table, xs[0], ys[0], streams[0], passes, out, ndev))
+    if args.dump_outputs:  # device 0's shard, before anything below overwrites it
+        with torch.cuda.device(devs[0]):
+            dump_outputs(args.dump_outputs, ys[0])
+    code = 0
+    if args.full:
+        # every device proves its shard, exactly as every rank does in the process-per-GPU form
+        recs, flags = [], [True, True]
+        for i, (d, pl, x, y, st) in enumerate(zip(devs, plans, xs, ys, streams)):
+            with torch.cuda.device(d):
+                v = verify_shard(torch, pl, x, y, p, st)
+            flags = [flags[0] and v["round_trip_identical"], flags[1] and v["coefficient_sum_invariant"]]
+            recs.append(dict(device_identity(torch, d), rank=i, ms_per_step=dev_ms[i], **v))
+        fields, code = verdict_fields(flags, recs, ndev, one_device_ok=rehearsal)
+        out.update(fields)
+        with torch.cuda.device(devs[0]), torch.cuda.stream(streams[0]):  # torch's own kernels (the device copy) on the launch stream too
+            code = max(code, rank0_extras(torch, args, plan0, table, xs[0], ys[0], streams[0], passes, out, ndev))
     emit(out, args)
     return code
 
@@ -1173,10 +1221,19 @@ def main():
     ap.add_argument("--rdzv-file", default=None,
                     help="rendezvous through this file (torch.distributed FileStore) instead of MASTER_ADDR / MASTER_PORT: no TCP "
                          "port to agree on; what `python bench.py --gpus N` uses for the ranks it starts itself")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, everything else the line reports: every rank's verification and device "
+                         "identity, the step-time distribution, the roofline, the CPU baseline, the inverse leg and BASELINE "
+                         "configs 2 / 4 / 5's shard (the --no-* switches above trim this mode); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's output (rank 0 / device 0) to DIR/<name>.npy as float64 "
+                         "halves of the words (dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.single_process:
         if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1:
             raise SystemExit("--single-process under a multi-rank launcher: start it as plain `python bench.py --gpus N --single-process`")
@@ -1259,26 +1316,33 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # no time without a check: every rank proves its own shard and says which device it ran on
-    v = verify_shard(torch, plan, x, y, p, stream)
-    # test hook, honoured in the one-device rehearsal only (NTT_BENCH_ONE_DEVICE=1): this rank REPORTS a failed check, so that the
-    # tests can watch one bad rank turn the line red; it can never turn a failure into a pass
-    if os.environ.get("NTT_BENCH_ONE_DEVICE") == "1" and os.environ.get("NTT_BENCH_INJECT_FAILURE") == str(rank):
-        v["round_trip_identical"] = False
-    ident = dict(device_identity(torch, local_rank), rank=rank, ms_per_step=own / args.steps * 1e3, **v)
-    reduced, recs = reduce_verdicts(dist, torch, dev, world, rank, [v["round_trip_identical"], v["coefficient_sum_invariant"]], ident)
-    fields, code = verdict_fields(reduced, recs, dist.get_world_size() if use_dist else 1,
-                                  one_device_ok=os.environ.get("NTT_BENCH_ONE_DEVICE") == "1")
+    if args.dump_outputs and rank == 0:  # rank 0's shard, before anything below overwrites it
+        dump_outputs(args.dump_outputs, y)
 
     total_ntt = batch * world * args.steps
     value = total_ntt / elapsed
     passes = plan.passes_for(batch)  # the decomposition the launcher picks for THIS batch (plan alternatives)
     out = base_line(args, logn, batch, world, value, elapsed, passes,
                     (dist.get_backend() if use_dist else "none (single process)"), "process-per-gpu")
-    out.update(fields)
+
+    code = 0
+    if args.full:
+        # no time without a check: every rank proves its own shard and says which device it ran on
+        v = verify_shard(torch, plan, x, y, p, stream)
+        # test hook, honoured in the one-device rehearsal only (NTT_BENCH_ONE_DEVICE=1): this rank REPORTS a failed check, so that
+        # the tests can watch one bad rank turn the line red; it can never turn a failure into a pass
+        if os.environ.get("NTT_BENCH_ONE_DEVICE") == "1" and os.environ.get("NTT_BENCH_INJECT_FAILURE") == str(rank):
+            v["round_trip_identical"] = False
+        ident = dict(device_identity(torch, local_rank), rank=rank, ms_per_step=own / args.steps * 1e3, **v)
+        reduced, recs = reduce_verdicts(dist, torch, dev, world, rank, [v["round_trip_identical"], v["coefficient_sum_invariant"]],
+                                        ident)
+        fields, code = verdict_fields(reduced, recs, dist.get_world_size() if use_dist else 1,
+                                      one_device_ok=os.environ.get("NTT_BENCH_ONE_DEVICE") == "1")
+        out.update(fields)
+        if rank == 0:
+            code = max(code, rank0_extras(torch, args, plan, eng.table, x, y, stream, passes, out, world))
 
     if rank == 0:
-        code = max(code, rank0_extras(torch, args, plan, eng.table, x, y, stream, passes, out, world))
         emit(out, args)
     if use_dist:
         dist.barrier()

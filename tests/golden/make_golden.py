@@ -108,6 +108,36 @@ def literal():
         barrett=np.array([R.ref_barrett_2k(int(a), int(b), q, w, u) for a, b in ab], dtype=np.int32))
 
 
+def literal_library():
+    """literal_lib_*.npz: the literal reference lines' answers to the exact inputs of the tests that compare against them
+    (tests/test_oracle.py, tests/test_host_cpu.py: literal_lib_oracle.npz; tests/test_gpu_parity.py: literal_lib_gpu.npz).
+    Per case "n<N>_p<P>_": g, table, in, stage<S> (the test_stage hook, test.cpp:55-58: S = logN-1 is the full network) and,
+    for the GPU cases, block16 of the full network; plus block_order_iota2048 (test.cpp:212-219 on 0..2047)."""
+    import oracle_py as O
+
+    if not O.have_ref():
+        print("literal reference not buildable here; skipping literal_lib_*.npz")
+        return
+    sets = {"oracle": (11, [(2, 3329, 3), (4, 3329, 3), (8, 3329, 3), (32, 3329, 3), (512, 12289, 11), (1024, 40961, 3),
+                            (2048, 3329, 3), (4096, 46337, 5)], lambda logn: {0, logn // 2, logn - 1}),
+            "gpu": (7, [(16, 3329, 3), (256, 3329, 3), (2048, 3329, 3), (4096, 12289, 11), (8192, 40961, 3), (1 << 14, 46337, 5)],
+                    lambda logn: {0, logn // 2, logn - 1})}
+    for name, (seed, cases, stages) in sets.items():
+        rng = np.random.default_rng(seed)
+        out = {"block_order_iota2048": O.ref_block_order(np.arange(2048, dtype=np.int32))}
+        for n, p, g in cases:
+            logn = n.bit_length() - 1
+            k = "n%d_p%d_" % (n, p)
+            a = rng.integers(0, p, size=n, dtype=np.int64).astype(np.int32)
+            out[k + "g"], out[k + "table"], out[k + "in"] = np.int64(g), O.ref_make_roots(n, p, g), a
+            for s in sorted(stages(logn)):
+                out[k + "stage%d" % s] = O.ref_ntt(a, out[k + "table"], p, s)
+            if name == "gpu":
+                out[k + "block16"] = O.ref_block_order(out[k + "stage%d" % (logn - 1)])
+        np.savez_compressed(os.path.join(HERE, "literal_lib_%s.npz" % name), **out)
+        print("literal_lib_%s: %d cases" % (name, len(cases)))
+
+
 def bigint(only_new=False):
     cases = [(64, 998244353, 3, 4), (1024, 998244353, 3, 4), (256, 3221225473, 5, 4),
              (64, GOLD, 7, 8), (1024, GOLD, 7, 8), (4096, GOLD, 7, 8),
@@ -130,6 +160,9 @@ def bigint(only_new=False):
 if __name__ == "__main__":
     if "--only-new" in sys.argv:  # add fixtures that do not exist yet, leave the committed ones byte-identical
         bigint(only_new=True)
+    elif "--literal-lib" in sys.argv:  # only the literal library's answers to the tests' own inputs
+        literal_library()
     else:
         literal()
+        literal_library()
         bigint()

@@ -355,3 +355,51 @@ def test_self_launch_ends_a_hung_job(tmp_path, monkeypatch):
     t0 = time.monotonic()
     rc = bench.self_launch(argparse.Namespace(gpus=2), [])
     assert rc == 124 and time.monotonic() - t0 < 40
+
+
+def test_dump_outputs_keeps_every_bit_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the last step's u64 words as two exact float64 halves; every row while they fit the budget, else a seeded
+    sample of rows (and of columns when one row alone exceeds it) that depends on the shape only; word 0 of every row."""
+    import torch
+
+    import bench
+
+    rng = np.random.default_rng(5)
+    y = torch.from_numpy(rng.integers(0, 2**64, size=(6, 64), dtype=np.uint64).view(np.int64))
+    bench.dump_outputs(str(tmp_path / "all"), y)
+
+    def load(d, name):
+        a = np.load(str(tmp_path / d / (name + ".npy")))
+        assert a.dtype == np.float64
+        return a
+
+    def words(d, what):
+        lo, hi = load(d, what + "_lo"), load(d, what + "_hi")
+        assert lo.max() < 2**32 and hi.max() < 2**32
+        return lo.astype(np.uint64) | (hi.astype(np.uint64) << np.uint64(32))
+
+    u = y.numpy().view(np.uint64)
+    assert np.array_equal(load("all", "forward_out_rows"), np.arange(6)) and np.array_equal(load("all", "forward_out_cols"), np.arange(64))
+    assert np.array_equal(words("all", "forward_out_rows"), u) and np.array_equal(words("all", "forward_out_word0"), u[:, 0])
+    # a budget of 3 rows: a sorted, seeded sample of rows, the same on every call
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 3 * 64 * 16)
+    bench.dump_outputs(str(tmp_path / "a"), y)
+    bench.dump_outputs(str(tmp_path / "b"), y)
+    rows = load("a", "forward_out_rows").astype(int)
+    assert len(rows) == 3 and list(rows) == sorted(set(rows)) and np.array_equal(rows, load("b", "forward_out_rows"))
+    assert np.array_equal(words("a", "forward_out_rows"), u[rows]) and np.array_equal(words("b", "forward_out_rows"), u[rows])
+    assert np.array_equal(words("a", "forward_out_word0"), u[:, 0])
+    # one row alone above the budget: one row, a seeded sample of its columns
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 16 * 16)
+    bench.dump_outputs(str(tmp_path / "c"), y)
+    rows, cols = load("c", "forward_out_rows").astype(int), load("c", "forward_out_cols").astype(int)
+    assert len(rows) == 1 and len(cols) == 16 and list(cols) == sorted(set(cols))
+    assert np.array_equal(words("c", "forward_out_rows"), u[rows][:, cols])
+
+
+def test_bench_rejects_a_step_count_below_one():
+    """--steps sets the number of timed steps; a run that would time none (and divide by zero) is refused before any work."""
+    import subprocess
+
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--steps must be >= 1" in out.stderr and "{" not in out.stdout

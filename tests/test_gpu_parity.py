@@ -338,7 +338,7 @@ def test_bench_json_contract():
     from conftest import ROOT
 
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                          "--batch", "64", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                          "--batch", "64", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -369,6 +369,50 @@ def test_bench_json_contract():
     assert "configs" not in d  # the extra configurations ride on the default shape only (batch 4096)
     assert r["frac_ceiling"] == pytest.approx(1.0 / r["passes"]) and r["frac"] <= r["frac_ceiling"]
     assert "valu" in r and "valu_source" in r and "inverse" in d and d["inverse"]["round_trip_identical"] is True
+
+
+def test_bench_plain_run_and_dump_outputs(oracle, tmp_path):
+    """A plain bench.py run times --steps steps and prints the headline keys alone (nothing --full measures); --dump-outputs
+    writes the last step's output words, which are the oracle's transform of the seeded inputs, and the same files from a
+    --full run of the same arguments."""
+    import json
+    import subprocess
+    import sys
+
+    import torch
+
+    import bench
+    from conftest import ROOT
+
+    def run(*extra):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--batch", "64"] + list(extra), capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+
+    d = run("--dump-outputs", str(tmp_path / "plain"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "NTT/s" and d["dtype"] == "u64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert not {"roofline", "ranks", "all_ranks_verified", "cpu_baseline", "inverse", "configs", "step_ms_median"} & set(d)
+    run("--dump-outputs", str(tmp_path / "full"), "--full", "--no-cpu-baseline", "--no-valu-floor")
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) and len(names) == 6
+    for name in names:
+        a, b = np.load(str(tmp_path / "plain" / name)), np.load(str(tmp_path / "full" / name))
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+
+    def words(what):
+        lo, hi = (np.load(str(tmp_path / "plain" / ("%s_%s.npy" % (what, h)))) for h in ("lo", "hi"))
+        return lo.astype(np.uint64) | (hi.astype(np.uint64) << np.uint64(32))
+
+    rows = np.load(str(tmp_path / "plain" / "forward_out_rows.npy")).astype(np.int64)
+    assert len(rows) >= 16 and np.array_equal(np.load(str(tmp_path / "plain" / "forward_out_cols.npy")), np.arange(1 << 16))
+    x = bench.synth_batch(torch, 64, 1 << 16, "cpu").numpy().view(np.uint64)
+    want = oracle.ntt(x[rows], oracle.make_roots(1 << 16, GOLD, 7, 8), GOLD, nthreads=8)
+    assert np.array_equal(words("forward_out_rows"), want)
+    assert np.array_equal(words("forward_out_word0"), oracle.ntt(x, oracle.make_roots(1 << 16, GOLD, 7, 8), GOLD, nthreads=8)[:, 0])
 
 
 @pytest.mark.parametrize("wb,p,g", [(8, GOLD, 7), (4, 3221225473, 5), (4, 998244353, 3)])
@@ -442,7 +486,7 @@ def test_bench_two_ranks_rehearsal():
     env.update(NTT_BENCH_ONE_DEVICE="1", NTT_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1", "--nproc-per-node", "2",
-         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "256"],
+         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "256", "--full"],
         capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -626,26 +670,27 @@ def test_randomized_differential(eng, oracle):
 
 def test_against_literal_reference_library(eng, oracle):
     """HIP path vs the COMPILED LITERAL reference lines (oracle/_ref/libntt_ref.so: src/test.cpp:15-60, 69-71,
-    212-219 built by oracle/build_ref.sh; the prebuilt library travels to the GPU box), inside the literal code's
-    validity window p <= 46340: table, full network, intermediate stages (test_stage hook) and block order."""
-    if not oracle.have_ref():
-        pytest.skip("literal reference library not present on this box")
-    rng = np.random.default_rng(7)
+    212-219 built by oracle/build_ref.sh; their answers to these inputs are recorded in tests/golden/literal_lib_gpu.npz by
+    make_golden.py --literal-lib), inside the literal code's validity window p <= 46340: table, full network, intermediate
+    stages (test_stage hook) and block order."""
+    f = np.load(os.path.join(GOLDEN, "literal_lib_gpu.npz"))
     for n, p, g in [(16, 3329, 3), (256, 3329, 3), (2048, 3329, 3), (4096, 12289, 11), (8192, 40961, 3), (1 << 14, 46337, 5)]:
         logn = n.bit_length() - 1
-        Tr = oracle.ref_make_roots(n, p, g)
+        k = "n%d_p%d_" % (n, p)
+        assert int(f[k + "g"]) == g
+        Tr = f[k + "table"]
         pl = eng.NTTPlan(logn, p, 4, 0)
         assert np.array_equal(pl.make_roots(g).astype(np.int64), Tr.astype(np.int64))
         pl.set_twiddles(Tr.astype(np.uint32))
-        a = rng.integers(0, p, size=n, dtype=np.int64)
+        a = f[k + "in"].astype(np.int64)
         d = eng.to_device(a.astype(np.uint32)[None, :], "cuda:0")
-        want = oracle.ref_ntt(a.astype(np.int32), Tr, p, logn - 1)
+        want = f[k + "stage%d" % (logn - 1)]
         assert np.array_equal(eng.to_host(pl.forward(d))[0].astype(np.int64), want.astype(np.int64)), (n, p)
         blk = eng.to_host(pl.forward(d, layout=eng.LAYOUT_AIE_BLOCK16))[0]
-        assert np.array_equal(blk.astype(np.int32), oracle.ref_block_order(want)), (n, p)
+        assert np.array_equal(blk.astype(np.int32), f[k + "block16"]), (n, p)
         for stage in {0, logn // 2}:
             got = eng.to_host(pl.forward_stages(d, stage))[0]
-            assert np.array_equal(got.astype(np.int64), oracle.ref_ntt(a.astype(np.int32), Tr, p, stage).astype(np.int64))
+            assert np.array_equal(got.astype(np.int64), f[k + "stage%d" % stage].astype(np.int64))
 
 
 def test_lazy_range_edges_small_moduli(eng, oracle):

@@ -272,7 +272,7 @@ def test_bench_self_launch_two_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--batch", "256"], capture_output=True, text=True, timeout=900, env=env)
+                          "--batch", "256", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-1000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -381,7 +381,7 @@ def test_bench_quotes_only_matching_forward_counters():
     from ntt_aie_amd import _lib
 
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
-                          "--no-valu-floor", "--no-inverse", "--explain"],  # --explain: the full provenance strings, not the slim line's file names
+                          "--no-valu-floor", "--no-inverse", "--explain", "--full"],  # --explain: the full provenance strings, not the slim line's file names
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

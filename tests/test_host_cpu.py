@@ -5,12 +5,16 @@ import pytest
 
 
 def test_block_order_matches_reference_rule(oracle):
+    import os
+
+    from conftest import GOLDEN
     from ntt_aie_amd import host
 
     a = np.arange(2048, dtype=np.uint32)
     assert np.array_equal(host.block_order(a), oracle.block16(a))
-    if oracle.have_ref():  # the literal src/test.cpp:212-219 loop
-        assert np.array_equal(host.block_order(a).astype(np.int32), oracle.ref_block_order(a.astype(np.int32)))
+    # the literal src/test.cpp:212-219 loop on the same input (recorded: tests/golden/make_golden.py --literal-lib)
+    want = np.load(os.path.join(GOLDEN, "literal_lib_oracle.npz"))["block_order_iota2048"]
+    assert np.array_equal(host.block_order(a).astype(np.int32), want)
     b = np.arange(2 * 64, dtype=np.uint64).reshape(2, 64)
     assert np.array_equal(host.block_order(b), oracle.block16(b))
     assert host.ANS_ORDER == oracle.ANS_ORDER

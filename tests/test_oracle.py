@@ -1,9 +1,9 @@
 """Pin the CPU restatement (oracle/ntt_oracle.c) before anything trusts it.
 
 Sources of truth, strongest first:
-  * oracle/_ref/libntt_ref.so -- the literal reference lines compiled where they
-    lie (only in the authoring container; skipped when absent),
-  * tests/golden/literal_*.npz -- outputs of that literal code, committed,
+  * tests/golden/literal_*.npz -- outputs of the literal reference lines (compiled where they lie into
+    oracle/_ref/libntt_ref.so by oracle/build_ref.sh), committed: literal_lib_*.npz hold its answers
+    to the very inputs of the tests that compare against it,
   * tests/golden/bigint_*.npz -- independent Python big-int restatement, for
     primes outside the literal int32 window,
   * the words SURVEY.md section 8(c) lists (T[1], out[0..7], ...).
@@ -85,23 +85,24 @@ def test_survey_kat_words(oracle):
 
 
 def test_restatement_vs_literal_library(oracle):
-    """Direct word-for-word comparison against the compiled literal lines."""
-    if not oracle.have_ref():
-        pytest.skip("reference tree absent: literal library not built")
-    rng = np.random.default_rng(11)
+    """Direct word-for-word comparison against the compiled literal lines' answers to these inputs
+    (literal_lib_oracle.npz, recorded by make_golden.py --literal-lib)."""
+    f = _load("literal_lib_oracle.npz")
     for n, p, g in [(2, 3329, 3), (4, 3329, 3), (8, 3329, 3), (32, 3329, 3), (512, 12289, 11),
                     (1024, 40961, 3), (2048, 3329, 3), (4096, 46337, 5)]:
         logn = n.bit_length() - 1
+        k = "n%d_p%d_" % (n, p)
+        assert int(f[k + "g"]) == g
         T = oracle.make_roots(n, p, g, 4)
-        Tr = oracle.ref_make_roots(n, p, g)
+        Tr = f[k + "table"]
         assert np.array_equal(T.astype(np.int64), Tr.astype(np.int64))
-        a = rng.integers(0, p, size=n, dtype=np.int64)
+        a = f[k + "in"].astype(np.int64)
         for stage in {0, logn // 2, logn - 1}:
             got = oracle.ntt(a.astype(np.uint32), T, p, stage=stage)
-            want = oracle.ref_ntt(a.astype(np.int32), Tr, p, stage)
+            want = f[k + "stage%d" % stage]
             assert np.array_equal(got.astype(np.int64), want.astype(np.int64)), (n, p, stage)
     a = np.arange(2048, dtype=np.int32)
-    assert np.array_equal(oracle.block16(a.astype(np.uint32)).astype(np.int32), oracle.ref_block_order(a))
+    assert np.array_equal(oracle.block16(a.astype(np.uint32)).astype(np.int32), f["block_order_iota2048"])
 
 
 def test_scalar_twins_fixture():

@@ -14,8 +14,8 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 SUM=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT" "$SUM"
 export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-valu-floor --no-configs"
-BENCH5="python3 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-valu-floor --no-configs"
+BENCH="python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-valu-floor --no-configs"
+BENCH5="python3 $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-valu-floor --no-configs"
 SQCNT="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE"
 # the weighted VALU model's inputs first: measured issue cost per instruction class, exact stream mix (stamped with the source hash)
 if [ -x "$ROOT/tools/valu_issue_cost" ]; then
@@ -25,7 +25,7 @@ fi
 python3 $ROOT/tools/valu_mix.py > "$SUM/${TAG}_valu_mix.json" 2> /dev/null
 cp "$SUM/${TAG}_valu_mix.json" "$ROOT/profiles/"
 cd /tmp
-python3 $ROOT/bench.py --explain > "$SUM/${TAG}_bench.json"   # the full line (explanatory keys kept: tools/design_table.py reads them); the driver runs the slim default
+python3 $ROOT/bench.py --full --explain > "$SUM/${TAG}_bench.json"   # the full line (explanatory keys kept: tools/design_table.py reads them)
 tail -c 600 "$SUM/${TAG}_bench.json"; echo
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- $BENCH > "$OUT/stats.log" 2>&1
 cp "$(find "$OUT/stats" -name '*kernel_stats.csv' | head -1)" "$SUM/${TAG}_kernel_stats.csv"
@@ -64,9 +64,9 @@ collect_config cfg4 10 3
 # the judged bench line once more, now that the counter summaries of THIS build exist (headline AND configs 2 / 4): bench.py quotes
 # roofline.traffic and the VALU counters only from profiles/<tag>_*.json stamped with the tree's kernel-source hash
 cd /tmp
-python3 $ROOT/bench.py --explain > "$SUM/${TAG}_bench.json"   # the full line (explanatory keys kept: tools/design_table.py reads them); the driver runs the slim default
+python3 $ROOT/bench.py --full --explain > "$SUM/${TAG}_bench.json"   # the full line (explanatory keys kept: tools/design_table.py reads them)
 tail -c 300 "$SUM/${TAG}_bench.json"; echo
-# ... and the line exactly as the driver gets it (no flags: numbers only, < 6 KB)
-python3 $ROOT/bench.py > "$SUM/${TAG}_bench_driver_line.json"
+# ... and its slim form (no --explain: numbers only, < 6 KB)
+python3 $ROOT/bench.py --full > "$SUM/${TAG}_bench_driver_line.json"
 wc -c "$SUM/${TAG}_bench_driver_line.json"
 ls -la "$SUM"

@@ -27,7 +27,7 @@ def summarize(path, batch=4096, logn=16, min_grid=1000000, src_hash=None):
         meta[pk["key"]] = pk
     out = {"src_hash": src_hash,
            "note": "rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU "
-                   "SQ_INSTS_VALU GRBM_GUI_ACTIVE -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-valu-floor (one pass, 8 SQ "
+                   "SQ_INSTS_VALU GRBM_GUI_ACTIVE -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-valu-floor (one pass, 8 SQ "
                    "slots); SQ_* cycle counters are quad-cycles summed over waves; GRBM_GUI_ACTIVE is summed over the 8 XCDs; means over the "
                    "batch-%d launches (N = 2^%d: batch * N/2 * LOG_M butterflies per launch, %d SIMDs); one entry per kernel instantiation, "
                    "keyed by the full PassCfg<...> argument list (INV = 5th argument); valu_frac_of_peak_all_vop3 = SQ_INSTS_VALU x %g cycles per "
