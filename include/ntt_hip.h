@@ -124,7 +124,9 @@ int ntt_plan_get_twiddles(ntt_plan_t plan, int inverse, void *host_T);
  * 256 + 16*a + k for alternative a: k = 0 number of passes, k = 1..7 stages in pass k-1,
  * k = 8..14 first stage of pass k-8, k = 15 the smallest batch this alternative is chosen for;
  * 512 + 16*a + k: the kernel variant of pass k of alternative a (0 = the default kernel of that pass shape; 1 = a single-pass
- * size of 2^10..2^12 words on twice the threads, chosen below the batch that fills the device) */
+ * size of 2^10..2^12 words on twice the threads, chosen below the batch that fills the device);
+ * 9 the coset blow-up log2 set by ntt_plan_set_coset (0 = not set), 10 whether ntt_lde on this plan expands inside its first
+ * pass (1) or runs the separate expansion kernel first (0; also 0 while no coset is set) */
 int64_t ntt_plan_info(ntt_plan_t plan, int what);
 
 /* The stage decomposition into HBM passes is chosen at LAUNCH, by batch size, among alternatives fixed at plan creation
@@ -155,6 +157,33 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out);
  * batch polynomials, contiguous. */
 int ntt_forward(ntt_plan_t plan, const void *d_in, void *d_out, size_t batch,
                 int out_layout, void *stream);
+
+/* ---- coset low-degree extension (no reference counterpart) --------------------
+ * The trace-commitment step of a STARK / Plonky2-style prover: from the N = M / 2^log_blowup coefficients of a polynomial P,
+ * its values on the coset shift * <w_M>, M = 2^logn of THIS plan (the size-M plan).
+ *
+ * ntt_plan_set_coset: plan configuration, like ntt_plan_set_policy -- call it before the plan is shared between host
+ * threads; calling it again replaces the setting.  log_blowup in [1, min(4, logn - 1)], shift in [1, p); anything else
+ * returns NTT_E_ARG.  Builds on the device (no host table) the plan-owned vector of N words s[i] = shift^bitrev_logN(i)
+ * mod p in the arithmetic's table form.  ntt_plan_clone copies the setting and the vector device-to-device;
+ * ntt_forward / ntt_inverse on a plan with a coset set are unaffected.
+ *
+ * ntt_lde: d_in is [batch][N] words, d_out [batch][M] words in `out_layout`.  Defined at network level, hence for any
+ * table:  d_out[b] = Forward_M(x_b),  x_b[i * 2^log_blowup] = d_in[b][i] * s[i] mod p,  every other word of x_b zero.
+ * With kind-1 (cyclic) tables of size N and M from the same generator, and d_in = ntt_inverse (scaled, natural layout) of
+ * the size-N plan applied to P's values on <w_N> -- the inverse network returns coefficients in bit-reversed order, and
+ * bitrev_M(j) = bitrev_N(j) * 2^log_blowup for j < N -- this is d_out[b][k] = P_b(shift * w_M^k) in natural order: no
+ * bit-reversal pass anywhere ("LDE").
+ * Asynchronous on `stream`; no allocation, no host synchronisation.  From logn = 5 on the expansion happens inside the
+ * first pass's load (nothing of size M is read or written before that pass's own store: N + M words of HBM traffic per row
+ * for the pass); smaller sizes run an expansion kernel first (ntt_plan_info 10).  The decomposition is the one
+ * ntt_plan_select(plan, batch) names, a pinned policy is honoured.  No access outside the caller's batch * N input words
+ * and batch * M output words.
+ * Errors: NTT_E_ARG for a null or misaligned pointer, batch out of range, a bad layout, no coset set, or when the byte
+ * ranges of d_in and d_out overlap (d_in != d_out always); NTT_E_NOTABLE before twiddles are set; NTT_E_LAYOUT as ntt_forward.
+ * batch == 0 is NTT_OK. */
+int ntt_plan_set_coset(ntt_plan_t plan, int log_blowup, uint64_t shift);
+int ntt_lde(ntt_plan_t plan, const void *d_in, void *d_out, size_t batch, int out_layout, void *stream);
 
 /* Profiling twin of ntt_forward (the reference brackets one kernel iteration with
  * trace events, src/aie_core.cc:129-131, src/aie2.py:168,316): identical launches

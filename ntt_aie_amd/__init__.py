@@ -5,7 +5,7 @@ src/test.cpp:115-190, src/aie2.py:320-337)."""
 from ._lib import (LAYOUT_AIE_BLOCK16, LAYOUT_NATURAL, LIB_PATH, NTTError)  # noqa: F401
 
 __all__ = ["NTTPlan", "MultiDevicePlan", "NTTError", "LAYOUT_NATURAL", "LAYOUT_AIE_BLOCK16", "GOLDILOCKS", "to_device",
-           "to_host", "version"]
+           "to_host", "lde_from_evals", "version"]
 
 
 def version() -> int:
@@ -14,7 +14,7 @@ def version() -> int:
 
 
 def __getattr__(name):
-    if name in ("NTTPlan", "GOLDILOCKS", "to_device", "to_host"):
+    if name in ("NTTPlan", "GOLDILOCKS", "to_device", "to_host", "lde_from_evals"):
         from . import plan
         return getattr(plan, name)
     if name == "MultiDevicePlan":

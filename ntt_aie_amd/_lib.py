@@ -35,6 +35,7 @@ LAYOUT_AIE_BLOCK16 = 1
 EXPORTS = (
     "ntt_version", "ntt_error_string", "ntt_device_count", "ntt_plan_create", "ntt_plan_destroy",
     "ntt_plan_set_twiddles", "ntt_make_roots", "ntt_make_table", "ntt_plan_generate_twiddles", "ntt_plan_get_twiddles", "ntt_plan_info", "ntt_plan_select", "ntt_plan_set_policy", "ntt_plan_clone", "ntt_forward",
+    "ntt_plan_set_coset", "ntt_lde",
     "ntt_forward_profile", "ntt_inverse", "ntt_pointwise_mul", "ntt_polymul_negacyclic", "ntt_count_noncanonical", "ntt_forward_stages",
 )
 
@@ -79,6 +80,9 @@ def open_library(path: str, since_v3: bool = True) -> C.CDLL:
         L.ntt_plan_set_policy.argtypes = [vp, C.c_int]
         L.ntt_plan_clone.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.ntt_forward.argtypes = [vp, vp, vp, sz, C.c_int, vp]
+    if hasattr(L, "ntt_lde"):  # (absent from the older builds tools/ time against the tree)
+        L.ntt_plan_set_coset.argtypes = [vp, C.c_int, u64]
+        L.ntt_lde.argtypes = [vp, vp, vp, sz, C.c_int, vp]
     L.ntt_forward_profile.argtypes = [vp, vp, vp, sz, C.c_int, vp, C.POINTER(C.c_float), C.c_int,
                                       C.POINTER(C.c_int)]
     L.ntt_inverse.argtypes = [vp, vp, vp, sz, C.c_int, C.c_int, vp]

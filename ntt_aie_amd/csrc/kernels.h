@@ -28,6 +28,9 @@ struct ErasedArgs {
     const void *skip_if;  // experiment build only: device word, non-zero = the launch is a no-op (fallback behind the fused kernel)
     int variant;          // PassDesc::variant (plan.h): 0 = the default kernel of this (contig, log_m); 1 = single-pass CONTIG unit of 10..12
                           // stages as radix-8 rounds in 512 threads (twice the waves per unit: small batches, one generation of workgroups)
+    const void *lde_in;   // forward CONTIG first pass of ntt_lde: compact source / coset vector / log2 blow-up (PassArgs::lde_*);
+    const void *lde_s;    // lde_beta == 0: an ordinary launch
+    int lde_beta;
 #if defined(NTT_PHASE_STAMPS)
     void *stamps;            // diagnostic build: PassArgs::stamps / stamp_records (ntt_stamps_set)
     uint32_t stamp_records;
@@ -81,6 +84,11 @@ hipError_t launch_gen_table_m32(void *T, int logn, int kind, uint32_t base_m, ui
                                 uint32_t pinv, uint32_t r2, hipStream_t s);
 hipError_t launch_gen_table_m64(void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, uint64_t p,
                                 uint64_t pinv, uint64_t r2, hipStream_t s);
+
+// coset vector of ntt_plan_set_coset: s[i] = shift^bitrev_logn(i mod 2^logn), table form, i < len (len = max(2^logn, 4))
+hipError_t launch_gen_coset(int fk, void *s_out, int logn, uint32_t len, uint64_t shift_m, uint64_t one_m, const ErasedArgs &field, hipStream_t s);
+// the separate expansion of ntt_lde: out[b][i << beta] = in[b][i] * s[i], zeros between; in: [batch][2^(n - beta)], out: [batch][2^n] words
+hipError_t launch_lde_expand(int fk, const void *in, const void *s_vec, void *out, int n, int beta, size_t batch, const ErasedArgs &field, hipStream_t s);
 
 // out[i] = T[i] * c (table form both): the N/2 scaled stage-0 twiddles of the Goldilocks inverse transform
 hipError_t launch_scale_table_gl(const void *T, void *out, size_t count, uint64_t c_m, hipStream_t s);

@@ -136,6 +136,50 @@ __global__ __launch_bounds__(256) void gen_table_kernel(typename F::W *T, int lo
     }
 }
 
+// Coset vector of a low-degree extension (ntt_plan_set_coset): s[i] = shift^bitrev_logn(i mod 2^logn) in table form, made on
+// the device like the twiddle tables (square-and-multiply per entry).  len = max(2^logn, 4): a vector shorter than one 16-byte
+// chunk of 4-byte words is stored periodically, so that the fused first pass reads it in whole chunks.
+template <class F>
+__global__ __launch_bounds__(256) void gen_coset_kernel(typename F::W *s, int logn, uint32_t len, typename F::W shift_m,
+                                                        typename F::W one_m, F f) {
+    using W = typename F::W;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x) {
+        uint32_t e = __brev(i & ((1u << logn) - 1u)) >> (32 - logn);  // logn >= 1
+        W r = one_m, b = shift_m;
+        while (e) {
+            if (e & 1u) r = f.mul(r, b);
+            b = f.mul(b, b);
+            e >>= 1;
+        }
+        s[i] = r;
+    }
+}
+
+// The separate expansion of ntt_lde (sizes without a fused first pass; the fused pass's comparator): one thread per 16-byte
+// chunk of the [batch][2^n] output, out[b][i << beta] = in[b][i] * s[i] and zero elsewhere, non-temporal 128-bit stores.
+// Word w of the output buffer is live when its low beta bits are clear, and then comes from compact word w >> beta.
+template <class F>
+__global__ __launch_bounds__(256) void lde_expand_kernel(const typename F::W *in, const typename F::W *sv, typename F::W *out,
+                                                         size_t chunks, int n, int beta, F f) {
+    using W = typename F::W;
+    constexpr int V = 16 / sizeof(W);
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    const size_t stride = (size_t) gridDim.x * blockDim.x;
+    const size_t live_mask = ((size_t) 1 << beta) - 1, row_mask = ((size_t) 1 << (n - beta)) - 1;
+    for (size_t c = (size_t) blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += stride) {
+        Vec<W, V> z;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const size_t w = c * V + k;
+            z.v[k] = (W) 0;
+            if ((w & live_mask) == 0) z.v[k] = f.mul(in[w >> beta], sv[(w >> beta) & row_mask]);
+        }
+        u32x4 zz;
+        __builtin_memcpy(&zz, &z, 16);
+        __builtin_nontemporal_store(zz, reinterpret_cast<u32x4 *>(out) + c);
+    }
+}
+
 // out[i] = T[i] * c, both in table (Montgomery) form: the scaled stage-0 twiddles of the inverse transform (pass.h: fold_scale)
 template <class F>
 __global__ __launch_bounds__(256) void scale_table_kernel(const typename F::W *T, typename F::W *out, size_t count,
@@ -208,6 +252,35 @@ hipError_t launch_gen_table_m64(void *T, int logn, int kind, uint64_t base_m, ui
                                 uint64_t pinv, uint64_t r2, hipStream_t s) {
     hipLaunchKernelGGL(gen_table_kernel<FieldM64>, dim3(grid_for((size_t) 1 << logn)), dim3(256), 0, s,
                        (uint64_t *) T, logn, kind, base_m, one_m, FieldM64{p, pinv, r2});
+    return hipGetLastError();
+}
+
+hipError_t launch_gen_coset(int fk, void *s_out, int logn, uint32_t len, uint64_t shift_m, uint64_t one_m, const ErasedArgs &e, hipStream_t s) {
+    const dim3 grid(grid_for(len)), block(256);
+    if (fk == 1)
+        hipLaunchKernelGGL(gen_coset_kernel<FieldGL>, grid, block, 0, s, (uint64_t *) s_out, logn, len, shift_m, one_m, FieldGL{});
+    else if (fk == 2)
+        hipLaunchKernelGGL(gen_coset_kernel<FieldM64>, grid, block, 0, s, (uint64_t *) s_out, logn, len, shift_m, one_m,
+                           FieldM64{e.p64, e.pinv64, e.r2_64});
+    else
+        hipLaunchKernelGGL(gen_coset_kernel<FieldM32>, grid, block, 0, s, (uint32_t *) s_out, logn, len, (uint32_t) shift_m, (uint32_t) one_m,
+                           FieldM32{e.p, e.pinv, e.r2});
+    return hipGetLastError();
+}
+
+hipError_t launch_lde_expand(int fk, const void *in, const void *s_vec, void *out, int n, int beta, size_t batch, const ErasedArgs &e, hipStream_t s) {
+    const size_t chunks = ((batch << n) * (fk == 0 ? 4 : 8)) / 16;  // 2^n words >= 16 bytes (n >= 2)
+    if (chunks == 0) return hipSuccess;
+    const dim3 grid(grid_for(chunks)), block(256);
+    if (fk == 1)
+        hipLaunchKernelGGL(lde_expand_kernel<FieldGL>, grid, block, 0, s, (const uint64_t *) in, (const uint64_t *) s_vec, (uint64_t *) out, chunks, n,
+                           beta, FieldGL{});
+    else if (fk == 2)
+        hipLaunchKernelGGL(lde_expand_kernel<FieldM64>, grid, block, 0, s, (const uint64_t *) in, (const uint64_t *) s_vec, (uint64_t *) out, chunks, n,
+                           beta, FieldM64{e.p64, e.pinv64, e.r2_64});
+    else
+        hipLaunchKernelGGL(lde_expand_kernel<FieldM32>, grid, block, 0, s, (const uint32_t *) in, (const uint32_t *) s_vec, (uint32_t *) out, chunks, n,
+                           beta, FieldM32{e.p, e.pinv, e.r2});
     return hipGetLastError();
 }
 

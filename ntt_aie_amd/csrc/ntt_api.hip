@@ -107,6 +107,11 @@ struct ntt_plan {
     std::vector<PassDesc> passes;  // = alts[0].passes: the default decomposition (ntt_plan_info 3 / 32+ / 64+)
     std::vector<PlanAlt> alts;     // launch-time alternatives, ascending min_batch (plan.h: plan_alternatives)
     int forced_alt;                // ntt_plan_set_policy: -1 = by batch, k >= 0 = always alternative k
+    // ntt_plan_set_coset: low-degree extension onto shift * <w_N> from N >> lde_beta coefficients (0 = not set)
+    int lde_beta;
+    uint64_t lde_shift;
+    void *d_lde_s;      // s[i] = shift^bitrev(i), table form, max(N >> lde_beta, 4) words (misc_kernels.hip: gen_coset_kernel)
+    int lde_unfused;    // experiment build only (NTT_LDE_UNFUSED=1): ntt_lde takes the separate expansion kernel at every size; 0 in the product
 };
 
 static_assert(NTT_E_NOMEM == NTT_E_NOMEM_GUARD && NTT_E_INTERNAL == NTT_E_INTERNAL_GUARD, "guard.h codes = include/ntt_hip.h codes");
@@ -123,6 +128,7 @@ void free_plan(ntt_plan *pl) {
     if (pl->d_tw_inv_sc) (void) hipFree(pl->d_tw_inv_sc);
     if (pl->d_fused_ctl) (void) hipFree(pl->d_fused_ctl);
     if (pl->d_counter) (void) hipFree(pl->d_counter);
+    if (pl->d_lde_s) (void) hipFree(pl->d_lde_s);
     delete pl;
 }
 // ntt_plan_create builds the plan under this holder: an exception (std::bad_alloc from the alternatives' vectors)
@@ -149,6 +155,13 @@ hipError_t launch_inv(const ntt_plan *pl, const PassDesc &pd, const ntt::ErasedA
 
 size_t table_bytes(const ntt_plan *pl) { return ((size_t) 1 << pl->logn) * pl->word_bytes; }
 size_t sc_table_bytes(const ntt_plan *pl) { return pl->word_bytes == 8 ? table_bytes(pl) / 2 : 0; }
+// words of the coset vector for a blow-up of 2^beta (kept periodic up to one 16-byte chunk of 4-byte words)
+size_t lde_s_words(const ntt_plan *pl, int beta) {
+    const size_t n = (size_t) 1 << (pl->logn - beta);
+    return n < 4 ? 4 : n;
+}
+// does ntt_lde expand inside the first pass of this plan (every alternative's first pass has >= 5 stages from logn = 5 on)
+bool lde_fused(const ntt_plan *pl) { return pl->lde_beta > 0 && pl->logn >= ntt::LDE_MIN_LOG_M && !pl->lde_unfused; }
 
 // the decomposition the launchers run for this batch
 const std::vector<PassDesc> &passes_for(const ntt_plan *pl, size_t batch) {
@@ -330,6 +343,10 @@ int ntt_plan_create(ntt_plan_t *out, int logn, uint64_t p, int word_bytes, int d
     pl->d_tw_fwd = pl->d_tw_inv = pl->d_tw_inv_sc = nullptr;
     pl->d_fused_ctl = nullptr;
     pl->d_counter = nullptr;
+    pl->d_lde_s = nullptr;
+    pl->lde_beta = 0;
+    pl->lde_shift = 0;
+    pl->lde_unfused = 0;
     pl->device = device;
     pl->logn = logn;
     pl->p = p;
@@ -373,6 +390,7 @@ int ntt_plan_create(ntt_plan_t *out, int logn, uint64_t p, int word_bytes, int d
     if (const char *e = getenv("NTT_ONLY_PASS")) pl->only_pass = atoi(e);
     if (const char *e = getenv("NTT_PASS_VARIANT")) pl->force_variant = atoi(e);
     if (const char *e = getenv("NTT_FUSED")) pl->fused = atoi(e);
+    if (const char *e = getenv("NTT_LDE_UNFUSED")) pl->lde_unfused = atoi(e) != 0;  // tools/bench_lde.py: leg B
     if (const char *e = getenv("NTT_PLAN_SPLIT")) {  // "8,6,6" = CONTIG 8 stages + two 6-stage column passes
         std::vector<PassDesc> v;
         int s0 = 0;
@@ -546,6 +564,8 @@ int64_t ntt_plan_info(ntt_plan_t pl, int what) NTT_GUARD {
         case 5: return pl->d_fused_ctl ? 1 : 0;
         case 6: return (int64_t) pl->alts.size();
         case 7: return pl->forced_alt;
+        case 9: return pl->lde_beta;
+        case 10: return lde_fused(pl) ? 1 : 0;
         case 8: {  // capacity for ntt_forward_profile whatever the batch
             size_t k = 0;
             for (const PlanAlt &a : pl->alts) k = a.passes.size() > k ? a.passes.size() : k;
@@ -591,6 +611,32 @@ int ntt_plan_set_policy(ntt_plan_t pl, int alternative) NTT_GUARD {
     return NTT_OK;
 } NTT_GUARD_END
 
+int ntt_plan_set_coset(ntt_plan_t pl, int log_blowup, uint64_t shift) NTT_GUARD {
+    if (!pl) return NTT_E_ARG;
+    const int max_beta = pl->logn - 1 < 4 ? pl->logn - 1 : 4;
+    if (log_blowup < 1 || log_blowup > max_beta) return NTT_E_ARG;
+    if (shift == 0 || shift >= pl->p) return NTT_E_ARG;
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    const size_t words = lde_s_words(pl, log_blowup);
+    void *d_s = nullptr;
+    hipError_t e = hipMalloc(&d_s, words * (size_t) pl->word_bytes);
+    if (e != hipSuccess) return (int) e;
+    const ntt::ErasedArgs fa = base_args(pl, pl->passes.front(), nullptr, nullptr, 0);  // the field's constants
+    e = ntt::launch_gen_coset(pl->fk, d_s, pl->logn - log_blowup, (uint32_t) words, to_table_form(shift, pl->p, pl->word_bytes),
+                              to_table_form(1 % pl->p, pl->p, pl->word_bytes), fa, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void) hipFree(d_s);
+        return (int) e;
+    }
+    if (pl->d_lde_s) (void) hipFree(pl->d_lde_s);  // a replaced setting (configuration call: nothing is in flight on this plan)
+    pl->d_lde_s = d_s;
+    pl->lde_beta = log_blowup;
+    pl->lde_shift = shift;
+    return NTT_OK;
+} NTT_GUARD_END
+
 int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
     if (!out) return NTT_E_ARG;
     *out = nullptr;
@@ -626,6 +672,23 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
         pl->has_table = true;
         pl->has_inv = src->has_inv;
     }
+    pl->lde_unfused = src->lde_unfused;
+    if (src->lde_beta > 0) {  // the coset setting and its vector, device to device like the tables
+        const size_t bytes = lde_s_words(src, src->lde_beta) * (size_t) src->word_bytes;
+        DeviceGuard g(device);
+        hipError_t e = g.err;
+        if (e == hipSuccess) e = hipMalloc(&pl->d_lde_s, bytes);
+        if (e == hipSuccess)
+            e = device == src->device ? hipMemcpy(pl->d_lde_s, src->d_lde_s, bytes, hipMemcpyDeviceToDevice)
+                                      : hipMemcpyPeer(pl->d_lde_s, device, src->d_lde_s, src->device, bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            (void) ntt_plan_destroy(pl);
+            return (int) e;
+        }
+        pl->lde_beta = src->lde_beta;
+        pl->lde_shift = src->lde_shift;
+    }
     *out = pl;
     return NTT_OK;
 } NTT_GUARD_END
@@ -640,6 +703,49 @@ int ntt_forward(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int 
     DeviceGuard g(pl->device);
     if (g.err != hipSuccess) return (int) g.err;
     return run_forward(pl, d_in, d_out, batch, out_layout, (hipStream_t) stream);
+} NTT_GUARD_END
+
+int ntt_lde(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int out_layout, void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_in, d_out, batch);
+    if (rc) return rc;
+    if (!pl->has_table) return NTT_E_NOTABLE;
+    if (pl->lde_beta == 0) return NTT_E_ARG;
+    if (out_layout != NTT_LAYOUT_NATURAL && out_layout != NTT_LAYOUT_AIE_BLOCK16) return NTT_E_ARG;
+    if (out_layout == NTT_LAYOUT_AIE_BLOCK16 && pl->logn < 4) return NTT_E_LAYOUT;
+    if (batch == 0) return NTT_OK;
+    const int beta = pl->lde_beta;
+    const uintptr_t in0 = (uintptr_t) d_in, in1 = in0 + ((batch << (pl->logn - beta)) * (size_t) pl->word_bytes);
+    const uintptr_t out0 = (uintptr_t) d_out, out1 = out0 + ((batch << pl->logn) * (size_t) pl->word_bytes);
+    if (in0 < out1 && out0 < in1) return NTT_E_ARG;  // the first pass writes rows of d_out while later workgroups still read d_in
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    hipStream_t s = (hipStream_t) stream;
+    RoctxRange whole("ntt_lde");
+    const std::vector<PassDesc> &passes = passes_for(pl, batch);
+    if (!lde_fused(pl)) {
+        // expansion as a launch of its own, then the ordinary transform in place
+        const ntt::ErasedArgs fa = base_args(pl, passes.front(), nullptr, nullptr, 0);
+        hipError_t e = ntt::launch_lde_expand(pl->fk, d_in, pl->d_lde_s, d_out, pl->logn, beta, batch, fa, s);
+        if (e != hipSuccess) return (int) e;
+        return run_forward(pl, d_out, d_out, batch, out_layout, s, nullptr, 1, &passes);
+    }
+    for (const PassDesc &pd : passes) {
+#if defined(NTT_EXPERIMENT)
+        if (pl->only_pass >= 0 && (int) (&pd - &passes.front()) != pl->only_pass) continue;  // timing experiment: outputs meaningless
+#endif
+        RoctxRange pass("lde pass", pd.contig, pd.s0, pd.log_m);
+        ntt::ErasedArgs a = base_args(pl, pd, d_out, d_out, batch);
+        if (&pd == &passes.front()) {  // expands while it loads: reads d_in (compact) only, writes d_out
+            a.lde_in = d_in;
+            a.lde_s = pl->d_lde_s;
+            a.lde_beta = beta;
+        }
+        a.tw = pl->d_tw_fwd;
+        a.layout = out_layout;
+        hipError_t e = launch_fwd(pl, pd, a, s);
+        if (e != hipSuccess) return (int) e;
+    }
+    return NTT_OK;
 } NTT_GUARD_END
 
 int ntt_forward_profile(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int out_layout,

@@ -117,7 +117,7 @@ NTT_HD void static_for(Fn &&f) {
 }
 
 template <class F_, int LOG_M_, int LOG_C_, bool CONTIG_, bool INV_, int PRELOAD_MASK_ = 0xF, int LOG_E_ = 4,
-          int LOG_NT_ = LOG_NT, bool ALLOW_DMA_ = true>
+          int LOG_NT_ = LOG_NT, bool ALLOW_DMA_ = true, bool LDE_ = false>
 struct PassCfg {
     using F = F_;
     using W = typename F::W;
@@ -185,7 +185,13 @@ struct PassCfg {
     // hand-off needs no barrier there either; the exchanges of the later rounds keep theirs.)
     // ALLOW_DMA_ = false: the same radix-8 kernel with the tile staged by ordinary loads (phase_linear),
     // which is where a fused pointwise product has room to multiply.
-    static constexpr bool DMA = ALLOW_DMA_ && CONTIG && !INV && R > 1 && LOG_E_ < 4 && sizeof(W) == 8;
+    static constexpr bool DMA = ALLOW_DMA_ && !LDE_ && CONTIG && !INV && R > 1 && LOG_E_ < 4 && sizeof(W) == 8;
+    // LDE_: the first pass of a coset low-degree extension (ntt_lde).  The tile is not read from `in` at all: the wave
+    // loads the 1 / 2^beta of it that is live from the compact [batch][N] source, multiplies by the plan's coset vector and
+    // spreads the products over its zero-filled LDS segment (phase_lde_*).  Ordinary loads only: such a configuration is
+    // never an LDS-DMA or a register-prefetch kernel, whatever its shape -- the rule is here, not in a launcher's habits.
+    static constexpr bool LDE = LDE_;
+    static_assert(!LDE_ || (CONTIG_ && !INV_ && R > 1), "the fused expansion lives in a forward CONTIG pass of two rounds or more");
     static constexpr int LDS_WORDS = LDS_WORDS_PADDED;
     // Register prefetch of the NEXT polynomial's tile (round 6, BASELINE config 2): the 4-byte 512-thread radix-8 kernels that run a
     // single-pass size (PassDesc::variant 1) stage their tile linearly by ordinary loads; with PREFETCH a thread requests its E words
@@ -193,7 +199,7 @@ struct PassCfg {
     // and commits them to LDS at the start of the next iteration -- the HBM latency of every polynomial but the first hides under
     // the previous one's butterflies, so a launch can stream TWO polynomials per workgroup through ONE generation of workgroups
     // (pass_geometry: one_generation_wgs) instead of leaving a quarter of them to a second generation.
-    static constexpr bool PREFETCH = NTT_PREFETCH_M32_WIDE && ALLOW_DMA_ && CONTIG && !INV && R > 1 && LOG_E_ < 4 && LOG_NT_ == 9 && sizeof(W) == 4;
+    static constexpr bool PREFETCH = NTT_PREFETCH_M32_WIDE && ALLOW_DMA_ && !LDE_ && CONTIG && !INV && R > 1 && LOG_E_ < 4 && LOG_NT_ == 9 && sizeof(W) == 4;
     // Most polynomials a workgroup streams through its resident twiddles (tools/ppw_sweep.py, N = 2^13 .. 2^17, batches
     // 2048 .. 16384): the 256-thread Goldilocks LDS-DMA first passes are fastest at 8 whatever the batch (16 costs 5-6 % at
     // batch 8192), the Goldilocks column passes at 4 (8 costs 4 %); the other kernels keep the workgroup-count rule alone.
@@ -284,6 +290,12 @@ struct PassArgs {
                    // timing experiments: 1 = every iteration re-reads polynomial group 0,
                    // 2 = skip the direct stores, 4 = every iteration stores to polynomial group 0
     W scale;
+    // Fused coset expansion (PassCfg::LDE kernels only; all three "off" = zero for every other launch).  Word idx of a row of
+    // the tile is lde_in[row * (N >> lde_beta) + (idx >> lde_beta)] * lde_s[idx >> lde_beta] when the low lde_beta bits of idx
+    // are clear and 0 otherwise; `in` is not read.
+    const W *lde_in = nullptr;  // compact source, [batch][N >> lde_beta] words
+    const W *lde_s = nullptr;   // coset vector, table form, max(N >> lde_beta, 4) words (periodic when shorter than 4)
+    int lde_beta = 0;           // log2 of the blow-up, 1..4
 #if defined(NTT_PHASE_STAMPS)
     unsigned long long *stamps;  // [stamp_records][STAMP_RECORD] 64-bit slots, one record per wave of the launch (null: stamps go to a dummy record)
     uint32_t stamp_records;
@@ -295,6 +307,7 @@ struct Ctx {
     using W = typename Cfg::W;
     W x[Cfg::E];
     W pre[Cfg::PREFETCH ? Cfg::E : 1];  // PassCfg::PREFETCH: the next polynomial's linear chunks, in flight during this one's rounds
+    W lde_s[Cfg::LDE ? Cfg::E / 2 : 1];  // PassCfg::LDE: this lane's words of the coset vector (the same for every polynomial)
     W tw[Cfg::R][Cfg::E > 1 ? Cfg::E - 1 : 1];
     uint32_t tid, bx, by;
     uint32_t pg_base;        // first polynomial group of this workgroup
@@ -716,11 +729,157 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t linear_rsrc(const typename Cfg
 using u32x4_t = unsigned int __attribute__((ext_vector_type(4)));
 #endif
 
+// ---- fused coset expansion (Cfg::LDE; ntt_lde's first pass) ---------------------------------------------------------------
+// The tile of a size-N pass (N = 2^a.n) is TILE_WORDS consecutive words of the [batch][N] buffer and starts at a multiple of
+// TILE_WORDS, so the words of it that are live -- index a multiple of B = 2^lde_beta -- are TILE_WORDS / B CONSECUTIVE words
+// of the compact [batch][N / B] source, starting at word tile0 / B; the same holds for the 64 * E words a wave stages.
+// A wave therefore reads its 64 * E / B compact words with 16-byte loads, lanes along consecutive chunks (chunk j * 64 + lane,
+// j < CMAX; at B = 8 half the lanes have one, at B = 16 a quarter), multiplies by its resident words of the coset vector and
+// scatters the products over its own zero-filled LDS segment: zero-fill and scatter are two LDS instructions of the same
+// wave, executed in order, and round 0 reads the segment exactly as after a linear copy.  Per polynomial the pass moves
+// N / B words in and N out; nothing of size N is read.  A compact chunk is wholly inside or wholly outside the caller's
+// batch * N / B words (N / B >= V words per row) -- except 4-byte rows of two words (N / B = 2: logN = 5, B = 16), which are
+// read word by word, each under its own bound.
+template <class Cfg>
+struct LdeGeom {
+    using W = typename Cfg::W;
+    using G = LinearGeom<Cfg>;
+    static constexpr int V = G::V;
+    static constexpr int CMAX = G::ITER / 2;  // chunks per lane at B = 2
+    static_assert(Cfg::E >= 2 * V && CMAX * V <= Cfg::E / 2, "Ctx::lde_s holds CMAX chunks");
+    int beta;
+    uint32_t wave_chunks;  // compact chunks of the wave's segment
+    uint32_t lane, wbase;
+    size_t cbase;          // first compact word of the tile
+    uint64_t total;        // words the caller owns in the compact source
+    bool by_word;          // rows shorter than a chunk
+    NTT_HD LdeGeom(const Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it) {
+        beta = a.lde_beta;
+        wave_chunks = (uint32_t) ((64 * Cfg::E / V) >> beta);
+        lane = c.tid & 63u;
+        wbase = (c.tid >> 6) << (6 + Cfg::LOG_E);
+        cbase = uniform_word<Cfg>(c, a, it) >> beta;
+        total = (uint64_t) a.batch << (a.n - beta);
+        by_word = (1u << (a.n - beta)) < (uint32_t) V;
+    }
+    NTT_HD uint32_t chunk(int j) const { return (uint32_t) j * 64u + lane; }
+    NTT_HD bool has(int j) const { return chunk(j) < wave_chunks; }
+    NTT_HD uint32_t cword(int j) const { return (wbase >> beta) + chunk(j) * V; }  // compact word of chunk j, from cbase
+    NTT_HD uint32_t tile_word(int j, int k) const { return wbase + ((chunk(j) * V + (uint32_t) k) << beta); }
+};
+
+// the lane's words of the coset vector: position in the row only, so they stay in registers across the batch loop
+template <class Cfg>
+NTT_HD void phase_lde_init(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
+    using L = LdeGeom<Cfg>;
+    const L g(c, a, 0);
+    const uint32_t n_small = 1u << (a.n - a.lde_beta);
+    const uint32_t mask = (n_small < 4u ? 4u : n_small) - 1u;  // the vector is stored periodically up to 4 words
+#pragma unroll
+    for (int j = 0; j < L::CMAX; ++j) {
+        const uint32_t si = ((uint32_t) g.cbase + g.cword(j)) & mask;
+#pragma unroll
+        for (int k = 0; k < L::V; ++k) c.lde_s[j * L::V + k] = (typename Cfg::W) 0;
+        if (!g.has(j)) continue;
+#if defined(__HIP_DEVICE_COMPILE__)
+        const Chunk<typename Cfg::W, L::V> ch = *reinterpret_cast<const Chunk<typename Cfg::W, L::V> *>(a.lde_s + si);
+#pragma unroll
+        for (int k = 0; k < L::V; ++k) c.lde_s[j * L::V + k] = ch.v[k];
+#else
+        for (int k = 0; k < L::V; ++k) c.lde_s[j * L::V + k] = a.lde_s[si + (uint32_t) k];
+#endif
+    }
+}
+
+// compact source -> c.x[0 .. CMAX * V): all requests before anything waits on one of them
+template <class Cfg>
+NTT_HD void phase_lde_issue(Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it) {
+    using L = LdeGeom<Cfg>;
+    using W = typename Cfg::W;
+    const L g(c, a, it);
+    const uint64_t rem = g.total - (uint64_t) g.cbase;  // > 0: the polynomial group exists
+#if defined(__HIP_DEVICE_COMPILE__)
+    // descriptor over [cbase, end of the caller's compact words): what lies beyond reads as zero (ragged last group)
+    const uint64_t rem_bytes = rem * sizeof(W);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *) (a.lde_in + g.cbase), 0,
+                                                                        rem_bytes > 0xFFFFFFFFull ? -1 : (int) (uint32_t) rem_bytes, 0x00020000);
+#pragma unroll
+    for (int j = 0; j < L::CMAX; ++j) {
+        const uint32_t voff = g.cword(j) * (uint32_t) sizeof(W);
+#pragma unroll
+        for (int k = 0; k < L::V; ++k) c.x[j * L::V + k] = (W) 0;
+        if (!g.has(j)) continue;
+        if constexpr (sizeof(W) == 4) {
+            if (g.by_word) {  // uniform
+#pragma unroll
+                for (int k = 0; k < L::V; ++k) c.x[j * L::V + k] = __builtin_amdgcn_raw_buffer_load_b32(rs, voff + 4u * (uint32_t) k, 0, Cfg::LIN_AUX);
+                continue;
+            }
+        }
+        const u32x4_t d = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, Cfg::LIN_AUX);
+        Chunk<W, L::V> v;
+        __builtin_memcpy(&v, &d, 16);
+#pragma unroll
+        for (int k = 0; k < L::V; ++k) c.x[j * L::V + k] = v.v[k];
+    }
+#else
+    for (int j = 0; j < L::CMAX; ++j) {
+        for (int k = 0; k < L::V; ++k) c.x[j * L::V + k] = (W) 0;
+        if (!g.has(j)) continue;
+        const uint64_t w0 = g.cword(j);
+        if (g.by_word) {
+            for (int k = 0; k < L::V; ++k)
+                if (w0 + (uint64_t) k < rem) c.x[j * L::V + k] = a.lde_in[g.cbase + w0 + (uint64_t) k];
+        } else if (w0 < rem) {  // the whole chunk is the caller's
+            const Chunk<W, L::V> v = *reinterpret_cast<const Chunk<W, L::V> *>(a.lde_in + g.cbase + w0);
+            for (int k = 0; k < L::V; ++k) c.x[j * L::V + k] = v.v[k];
+        }
+    }
+#endif
+}
+
+// the wave's LDS segment := 0 (16-byte stores, the linear copy's own addresses) ...
+template <class Cfg>
+NTT_HD void phase_lde_zero(Ctx<Cfg> &c, const PassArgs<Cfg> &a, typename Cfg::W *lds, int it) {
+    using G = LinearGeom<Cfg>;
+    using Ch = typename G::Ch;
+    const G g(c, a, it);
+    Ch z;
+#pragma unroll
+    for (int k = 0; k < G::V; ++k) z.v[k] = (typename Cfg::W) 0;
+#pragma unroll
+    for (int i = 0; i < G::ITER; ++i) {
+        for (int k = 0; k < G::V; ++k) NTT_LDS_ACCESS(lds + g.lds(i) + k, c.tid, true);
+        *reinterpret_cast<Ch *>(lds + g.lds(i)) = z;
+    }
+}
+
+// ... then the live words: compact word * coset word, at every 2^beta-th place of the segment
+template <class Cfg>
+NTT_HD void phase_lde_scatter(Ctx<Cfg> &c, const PassArgs<Cfg> &a, typename Cfg::W *lds, int it) {
+    using L = LdeGeom<Cfg>;
+    const L g(c, a, it);
+#pragma unroll
+    for (int j = 0; j < L::CMAX; ++j) {
+        if (!g.has(j)) continue;
+#pragma unroll
+        for (int k = 0; k < L::V; ++k) {
+            typename Cfg::W *p = lds + Cfg::lds_index(g.tile_word(j, k));
+            NTT_LDS_ACCESS(p, c.tid, true);
+            *p = a.field.mul(c.x[j * L::V + k], c.lde_s[j * L::V + k]);
+        }
+    }
+}
+
 // HBM -> registers: ALL the tile's chunks of this thread are requested before anything waits on one of them (c.x is the
 // staging set: chunk i in x[i*V .. i*V+V)); with a fused pointwise product (a.in2, the negacyclic product's middle leg)
 // the second operand's chunks follow and the products replace the staged words.
 template <class Cfg>
 NTT_HD void phase_linear_issue(Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it, bool to_pre = false) {
+    if constexpr (Cfg::LDE) {  // the tile comes from the compact source
+        phase_lde_issue<Cfg>(c, a, it);
+        return;
+    }
     using G = LinearGeom<Cfg>;
     using Ch = typename G::Ch;
     const G g(c, a, it);
@@ -1189,6 +1348,7 @@ NTT_HD void run_pass(Exec &ex, const PassArgs<Cfg> &a) {
     // that load straight into the round registers measured neutral to +3 % on 4-byte words and costs the 8-byte column
     // pass 2 VGPRs beyond 128: not done.)  Exec::early_ok = false (tools-side fused schedule) keeps the old order.
     constexpr bool EARLY_LOAD = Exec::early_ok && !Cfg::DIRECT_LOAD && !Cfg::DMA;
+    static_assert(!Cfg::LDE || (!Cfg::DIRECT_LOAD && !Cfg::DMA && !Cfg::PREFETCH), "fused expansion: a linearly staged tile, ordinary loads");
     if constexpr (EARLY_LOAD) ex.init_indices(a);
     else ex.init(a);
     auto group_valid = [&](int it) {  // uniform: does polynomial group `it` of this workgroup exist
@@ -1198,6 +1358,7 @@ NTT_HD void run_pass(Exec &ex, const PassArgs<Cfg> &a) {
         if (group_valid(0)) ex.each([&](C &c) { phase_begin_iter<Cfg>(c, a, 0); phase_linear_issue<Cfg>(c, a, 0); });
         ex.each([&](C &c) { phase_init_twiddles<Cfg>(c, a); });
     }
+    if constexpr (Cfg::LDE) ex.each([&](C &c) { phase_lde_init<Cfg>(c, a); });
     if constexpr (Cfg::DMA) {
         if (group_valid(0)) ex.each([&](C &c) { phase_dma_issue<Cfg>(c, a, ex.lds(), 0); });
     }
@@ -1224,7 +1385,12 @@ NTT_HD void run_pass(Exec &ex, const PassArgs<Cfg> &a) {
         } else {
             const bool prefetched = Cfg::PREFETCH && it > 0;  // (uniform) this tile's chunks were requested during the previous iteration
             if (!prefetched && (!EARLY_LOAD || it > 0)) ex.each([&](C &c) { phase_linear_issue<Cfg>(c, a, it); });
-            ex.each([&](C &c) { phase_linear_commit<Cfg>(c, a, tile, it, prefetched); });
+            if constexpr (Cfg::LDE) {
+                ex.each([&](C &c) { phase_lde_zero<Cfg>(c, a, tile, it); });
+                ex.each([&](C &c) { phase_lde_scatter<Cfg>(c, a, tile, it); });
+            } else {
+                ex.each([&](C &c) { phase_linear_commit<Cfg>(c, a, tile, it, prefetched); });
+            }
             // round 0 of thread t reads words [E*t, E*t + E) of the tile: the segment its own wave has just staged, so this
             // hand-off is wave-local whatever the unit size (as with the LDS-DMA tiles); the later exchanges keep their barrier
             ex.sync(std::integral_constant<bool, FIRST == 0 || Cfg::WAVE_LOCAL>{});  // (an inverse pass staged this way is a small, wave-local unit)
@@ -1448,6 +1614,65 @@ struct ProductCfgM32 {
     using CI = PassCfg<FieldM32, LOG_M, 0, true, true, 1, 4, LOG_NT, false>;
     using CF = PassCfg<FieldM32, LOG_M, 0, true, false, 1, 4, LOG_NT, false>;
 };
+
+// The fused-expansion twin (PassCfg::LDE) of the forward CONTIG pass of 2^log_m words that a plan runs as its FIRST pass:
+// the same radix, workgroup size and resident-twiddle policy as the plain kernel of that shape (pass_kernel.inc), staged by
+// ordinary loads.  One rule for the launcher and for the host index model: fn(Tag<Cfg>{}) is called with the configuration,
+// false = no such pass (log_m < 5 has a single register round and keeps the separate expansion kernel).
+// A fused operand keeps the default kernel of the shape, as the fused pointwise product does (PassDesc::variant is not consulted).
+template <class Cfg_>
+struct CfgTag {
+    using Cfg = Cfg_;
+};
+template <class F, class Fn>
+bool lde_dispatch(int log_m, bool last_pass, Fn &&fn) {
+    constexpr int WB = (int) sizeof(typename F::W);
+    auto r16 = [&](auto mm) {
+        constexpr int M = decltype(mm)::value;
+        fn(CfgTag<PassCfg<F, M, 0, true, false, contig_preload_mask(M, WB), 4, LOG_NT, true, true>>{});
+        return true;
+    };
+    auto r8 = [&](auto mm) {
+        constexpr int M = decltype(mm)::value;
+        fn(CfgTag<PassCfg<F, M, 0, true, false, 0xF, 3, M >= 10 ? 9 : 8, true, true>>{});
+        return true;
+    };
+    if (log_m == 13) {
+        fn(CfgTag<PassCfg<F, 13, 0, true, false, WB == 4 ? 0xF : 0x8, 4, 9, true, true>>{});
+        return true;
+    }
+    if (log_m == 14) {
+        if constexpr (WB == 4) {
+            fn(CfgTag<PassCfg<F, 14, 0, true, false, 0xF, 4, 10, true, true>>{});
+            return true;
+        } else {
+            return false;
+        }
+    }
+    if (contig_log_e(log_m, WB, last_pass) == 3) {
+        switch (log_m) {
+            case 7: return r8(std::integral_constant<int, 7>{});
+            case 8: return r8(std::integral_constant<int, 8>{});
+            case 9: return r8(std::integral_constant<int, 9>{});
+            case 10: return r8(std::integral_constant<int, 10>{});
+            case 11: return r8(std::integral_constant<int, 11>{});
+            case 12: return r8(std::integral_constant<int, 12>{});
+            default: return false;
+        }
+    }
+    switch (log_m) {
+        case 5: return r16(std::integral_constant<int, 5>{});
+        case 6: return r16(std::integral_constant<int, 6>{});
+        case 7: return r16(std::integral_constant<int, 7>{});
+        case 8: return r16(std::integral_constant<int, 8>{});
+        case 9: return r16(std::integral_constant<int, 9>{});
+        case 10: return r16(std::integral_constant<int, 10>{});
+        case 11: return r16(std::integral_constant<int, 11>{});
+        case 12: return r16(std::integral_constant<int, 12>{});
+        default: return false;
+    }
+}
+constexpr int LDE_MIN_LOG_M = 5;  // smallest first pass with a fused twin (= smallest logN whose ntt_lde is fused)
 
 // ---- launch geometry shared by host planner and host model ---------------------
 struct PassGeom {

@@ -158,6 +158,14 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
     a.in2 = (const W *) e.in2;
     a.pw_scale = (W) e.pw_scale;
     a.skip_if = (const uint32_t *) e.skip_if;
+    // the fused expansion runs in its own kernels and nowhere else (never beside LDS-DMA or the register prefetch: PassCfg::LDE)
+    if ((e.lde_beta != 0) != Cfg::LDE) return hipErrorInvalidValue;
+    if constexpr (Cfg::LDE) {
+        if (e.lde_beta < 1 || e.lde_beta > 4 || e.lde_beta >= e.n || e.s0 != 0 || !e.lde_in || !e.lde_s || e.in2) return hipErrorInvalidValue;
+        a.lde_in = (const W *) e.lde_in;
+        a.lde_s = (const W *) e.lde_s;
+        a.lde_beta = e.lde_beta;
+    }
 #if defined(NTT_PHASE_STAMPS)
     a.stamps = (unsigned long long *) e.stamps;
     a.stamp_records = e.stamp_records;
@@ -187,6 +195,7 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
             sub.in = (const char *) e.in + off;
             sub.out = (char *) e.out + off;
             if (e.in2) sub.in2 = (const char *) e.in2 + off;
+            if (e.lde_beta) sub.lde_in = (const char *) e.lde_in + (off >> e.lde_beta);
             sub.batch = (uint32_t) (e.batch - done < slice ? e.batch - done : slice);
             const hipError_t err = launch_cfg<Cfg>(sub, s);
             if (err != hipSuccess) return err;
@@ -236,6 +245,16 @@ using ColCfg = ColPassCfg<NTT_FIELD, LOG_M, NTT_INV>;
 }  // namespace
 
 hipError_t NTT_LAUNCH_FN(bool contig, int log_m, const ErasedArgs &a, hipStream_t s) {
+    if (a.lde_beta != 0) {  // first pass of ntt_lde: the fused-expansion twin of this shape (pass.h: lde_dispatch)
+        if constexpr (NTT_INV) {
+            return hipErrorInvalidValue;
+        } else {
+            hipError_t err = hipErrorInvalidValue;
+            if (!contig || !lde_dispatch<NTT_FIELD>(log_m, a.s0 + log_m == a.n, [&](auto tag) { err = launch_cfg<typename decltype(tag)::Cfg>(a, s); }))
+                return hipErrorInvalidValue;
+            return err;
+        }
+    }
     if (contig) {
         if (log_m == 13) return launch_cfg<ContigCfg13>(a, s);
         if (log_m == 14) {

@@ -51,6 +51,12 @@ class MultiDevicePlan:
     def make_table(self, kind: int, g: int) -> np.ndarray:
         return self.plans[0].make_table(kind, g)
 
+    def set_coset(self, log_blowup: int, shift: int) -> None:
+        """NTTPlan.set_coset on the first plan; the clones carry the setting and the vector (ntt_plan_clone)."""
+        self.plans[0].set_coset(log_blowup, shift)
+        if self._cloned:
+            self._clone_all()
+
     # ---- shards -------------------------------------------------------------------------------------------------------
     def rows(self, batch: int) -> list[tuple[int, int]]:
         """Row range [lo, hi) of the [batch][N] job held by each device (contiguous, sizes differ by at most one)."""
@@ -95,6 +101,20 @@ class MultiDevicePlan:
     def inverse(self, shards: list[torch.Tensor], outs: list[torch.Tensor] | None = None, layout: int = LAYOUT_NATURAL,
                 scale: bool = True):
         return self._each(lambda pl, x, y, st: pl.inverse(x, y, layout=layout, scale=scale, stream=st), shards, outs)
+
+    def lde(self, shards: list[torch.Tensor], outs: list[torch.Tensor] | None = None, layout: int = LAYOUT_NATURAL):
+        """NTTPlan.lde by rows: shard i is [rows_i][N >> log_blowup] words on device i, the result [rows_i][N]."""
+        beta = self.plans[0].log_blowup
+
+        def empty_out(pl, x, st):
+            with torch.cuda.device(pl.device), torch.cuda.stream(st):
+                return torch.empty((0 if beta == 0 else x.numel() // (self.n >> beta), self.n), dtype=x.dtype, device=x.device)
+
+        if outs is None:
+            outs = [None] * len(shards)
+        # (a device whose shard is empty gets an empty [0][N] result, not its input back)
+        outs = [y if (y is not None or x.shape[0]) else empty_out(pl, x, st) for pl, st, x, y in zip(self.plans, self.streams, shards, outs)]
+        return self._each(lambda pl, x, y, st: pl.lde(x, y, layout=layout, stream=st), shards, outs)
 
     def close(self) -> None:
         for pl in self.plans:

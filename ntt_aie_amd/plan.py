@@ -146,6 +146,22 @@ class NTTPlan:
         check(_lib.lib().ntt_plan_clone(self._h, device, C.byref(new._h)), "ntt_plan_clone")
         return new
 
+    # ---- coset low-degree extension (this plan is the size-M one) ------------------
+    def set_coset(self, log_blowup: int, shift: int) -> None:
+        """Configure lde(): N = M >> log_blowup coefficients in, values on shift * <w_M> out (ntt_plan_set_coset).  The plan builds
+        its N-word vector shift^bitrev(i) on the device.  Configuration: call before the plan is shared between threads."""
+        check(_lib.lib().ntt_plan_set_coset(self._h, log_blowup, shift), "ntt_plan_set_coset")
+
+    @property
+    def log_blowup(self) -> int:
+        """log2 of the blow-up set by set_coset(); 0 = not set."""
+        return int(_lib.lib().ntt_plan_info(self._h, 9))
+
+    @property
+    def lde_fused(self) -> bool:
+        """Does lde() expand inside the first pass (True from logn = 5 on) or through the separate expansion kernel."""
+        return bool(_lib.lib().ntt_plan_info(self._h, 10))
+
     @property
     def has_inverse(self) -> bool:
         return bool(_lib.lib().ntt_plan_info(self._h, 4))
@@ -190,6 +206,30 @@ class NTTPlan:
         b = self._batch(inp, out)
         check(_lib.lib().ntt_forward(self._h, inp.data_ptr(), out.data_ptr(), b, layout,
                                      self._stream(stream)), "ntt_forward")
+        return out
+
+    def lde(self, inp: torch.Tensor, out: torch.Tensor | None = None, layout: int = LAYOUT_NATURAL, stream=None) -> torch.Tensor:
+        """Low-degree extension (ntt_lde): `inp` is [batch][N] words, N = M >> log_blowup, in the order inverse() of the size-N
+        plan returns them; the result is [batch][M].  `out` must not overlap `inp`."""
+        beta = self.log_blowup
+        if beta == 0:
+            raise ValueError("set_coset() first")
+        n_small = self.n >> beta
+        if not inp.is_cuda or inp.device.index != self.device:
+            raise ValueError("buffer is not on cuda:%d" % self.device)
+        if not inp.is_contiguous() or inp.element_size() != self.word_bytes or inp.numel() % n_small:
+            raise ValueError("input must be contiguous [batch][%d] %d-byte words" % (n_small, self.word_bytes))
+        b = inp.numel() // n_small
+        if out is None:
+            if stream is None:
+                out = torch.empty((b, self.n), dtype=inp.dtype, device=inp.device)
+            else:  # allocated under the launch stream, as _out_like does
+                st = stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream), device=inp.device)
+                with torch.cuda.stream(st):
+                    out = torch.empty((b, self.n), dtype=inp.dtype, device=inp.device)
+        if self._batch(out) != b:
+            raise ValueError("output must be [batch][%d] words for %d input rows" % (self.n, b))
+        check(_lib.lib().ntt_lde(self._h, inp.data_ptr(), out.data_ptr(), b, layout, self._stream(stream)), "ntt_lde")
         return out
 
     def forward_profile(self, inp: torch.Tensor, out: torch.Tensor | None = None,
@@ -243,3 +283,15 @@ class NTTPlan:
         check(_lib.lib().ntt_forward_stages(self._h, inp.data_ptr(), out.data_ptr(), b, stage,
                                             self._stream(stream)), "ntt_forward_stages")
         return out
+
+
+def lde_from_evals(small_plan: NTTPlan, big_plan: NTTPlan, evals: torch.Tensor, out: torch.Tensor | None = None,
+                   layout: int = LAYOUT_NATURAL, stream=None, coeffs: torch.Tensor | None = None) -> torch.Tensor:
+    """Values of each row's polynomial on the coset big_plan was configured for (set_coset), from its values on <w_N>.
+    small_plan (size N) and big_plan (size M = N << log_blowup) hold kind-1 tables from the same generator.  Two steps: the scaled
+    inverse at size N (coefficients, in the bit-reversed order the network returns) and big_plan.lde(); `coeffs` is an optional
+    [batch][N] scratch buffer for the coefficients (default: allocated; pass `evals` itself to transform in place)."""
+    if small_plan.logn + big_plan.log_blowup != big_plan.logn or small_plan.p != big_plan.p or small_plan.word_bytes != big_plan.word_bytes:
+        raise ValueError("plans do not match: need logn_small + log_blowup == logn_big, same modulus and word size")
+    c = small_plan.inverse(evals, coeffs, scale=True, stream=stream)
+    return big_plan.lde(c, out, layout=layout, stream=stream)
