@@ -1,0 +1,242 @@
+// launch.h -- which kernel runs for a pass, and with which arguments: the field descriptor, the type-erased launch
+// arguments, the selection rules and the ErasedArgs -> PassArgs<Cfg> fill.  Host code only (no hip_runtime.h): the GPU
+// launchers (pass_kernel.inc, product_kernel.inc, misc_kernels.hip) and the host index model (tests/emu, plain g++)
+// both go through here, so what the CPU suite steps is what the GPU launches.
+#pragma once
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "pass.h"
+#include "plan.h"
+
+namespace ntt {
+
+// arithmetic of a plan: FieldM32 (4-byte words), FieldGL (p = 2^64 - 2^32 + 1), FieldM64 (any other odd 8-byte modulus)
+enum FieldKind { FK_M32 = 0, FK_GL = 1, FK_M64 = 2 };
+struct FieldParams {
+    FieldKind kind;
+    uint64_t p, pinv, r2;  // modulus and its Montgomery constants (pinv, r2: 0 for Goldilocks, which has none)
+};
+inline FieldParams field_params(int word_bytes, uint64_t p) {
+    if (word_bytes == 4) return {FK_M32, p, host::mont_pinv((uint32_t) p), host::mont_r2((uint32_t) p)};
+    if (p == host::GOLDILOCKS) return {FK_GL, p, 0, 0};
+    return {FK_M64, p, host::mont_pinv64(p), host::mont_r2_64(p)};
+}
+inline int field_word_bytes(const FieldParams &fp) { return fp.kind == FK_M32 ? 4 : 8; }
+template <class F>
+F make_field(const FieldParams &fp) {
+    using W = typename F::W;
+    if constexpr (std::is_same<F, FieldGL>::value) return FieldGL{};
+    else return F{(W) fp.p, (W) fp.pinv, (W) fp.r2};
+}
+// fn(field object of the plan's arithmetic); the one place a FieldKind turns into a type
+template <class Fn>
+auto with_field(const FieldParams &fp, Fn &&fn) {
+    if (fp.kind == FK_GL) return fn(make_field<FieldGL>(fp));
+    if (fp.kind == FK_M64) return fn(make_field<FieldM64>(fp));
+    return fn(make_field<FieldM32>(fp));
+}
+
+struct ErasedArgs {
+    const void *in;
+    void *out;
+    const void *tw;
+    const void *tw_sc;     // scaled inverse, 8-byte CONTIG pass: stage-0 twiddles * N^-1 (PassArgs::tw_sc); null = phase_scale
+    FieldParams field;
+    int n, s0;
+    uint32_t batch;
+    int layout;
+    int do_scale;
+    uint64_t scale;  // table form
+    uint32_t target_wgs;
+    int dbg;  // timing experiments (NTT_DEBUG_FLAGS), 0 in production
+    const void *tw2;     // product_mid launch: the FORWARD table (tw is the inverse one there)
+    const void *in2;     // forward CONTIG pass: second operand of a fused pointwise product (or null)
+    uint64_t pw_scale;   // scale * R^2 (see PassArgs::pw_scale)
+    const void *skip_if;  // experiment build only: device word, non-zero = the launch is a no-op (fallback behind the fused kernel)
+    int variant;          // PassDesc::variant (plan.h): 0 = the default kernel of this (contig, log_m); 1 = single-pass CONTIG unit of 10..12
+                          // stages as radix-8 rounds in 512 threads (twice the waves per unit: small batches, one generation of workgroups)
+    const void *lde_in;   // forward CONTIG first pass of ntt_lde: compact source / coset vector / log2 blow-up (PassArgs::lde_*);
+    const void *lde_s;    // lde_beta == 0: an ordinary launch
+    int lde_beta;
+#if defined(NTT_PHASE_STAMPS)
+    void *stamps;            // diagnostic build: PassArgs::stamps / stamp_records (ntt_stamps_set)
+    uint32_t stamp_records;
+#endif
+};
+
+// ---- the pass kernels of one (field, direction) ------------------------------------------------------------------
+template <class F, int LOG_M, bool INV>
+using ContigCfg = PassCfg<F, LOG_M, 0, true, INV, contig_preload_mask(LOG_M, sizeof(typename F::W))>;
+// 13 stages on an 8192-word tile: 512 threads x 16 words, rounds of 4 + 4 + 4 + 1 stages.  4-byte words keep every round's
+// twiddles in registers (99 VGPRs); 8-byte words only the last round's single, wave-uniform one (the others are re-read
+// from L2 at the start of their round, as in the 12-stage radix-16 pass: 128 VGPRs, two workgroups per CU)
+template <class F, bool INV>
+using ContigCfg13 = PassCfg<F, 13, 0, true, INV, sizeof(typename F::W) == 4 ? 0xF : 0x8, 4, 9>;
+// 14 stages on a 16384-word tile of 4-byte words (64 KiB): ONE 1024-thread workgroup per CU, rounds of 4 + 4 + 4 + 2 stages, every
+// round's twiddles resident.  Pays only for the lazy butterflies (p < 2^30: N = 2^14 in one pass -21 % forward, -5 % inverse at
+// saturating batches; +3 % for a 32-bit prime, +20 % for one polynomial: profiles/r02_ab_13_stage_pass.txt), so the planner offers it
+// as a launch-time alternative for that modulus class above a batch threshold (plan.h: plan_alternatives)
+template <class F, bool INV>
+using ContigCfg14 = PassCfg<F, 14, 0, true, INV, 0xF, 4, 10>;
+// radix-8 rounds: 256 threads up to 9 stages, 512 threads for 10..12.  ALLOW_DMA = false: the same kernel with the tile staged
+// by ordinary loads, which is where a fused pointwise product (a.in2) has room to multiply
+template <class F, int LOG_M, bool INV, bool ALLOW_DMA = true>
+using ContigCfgE8 = PassCfg<F, LOG_M, 0, true, INV, 0xF, 3, LOG_M >= 10 ? 9 : 8, ALLOW_DMA>;
+
+// fn(std::integral_constant<int, M>{}) for the M in [LO, HI] that equals log_m; false = none does
+template <int LO, int HI, class Fn>
+bool with_log_m(int log_m, Fn &&fn) {
+    if constexpr (LO > HI) {
+        return false;
+    } else {
+        if (log_m != LO) return with_log_m<LO + 1, HI>(log_m, fn);
+        fn(std::integral_constant<int, LO>{});
+        return true;
+    }
+}
+
+// THE selection rule: fn(CfgTag<Cfg>{}) with the configuration of the pass kernel that runs stages [a.s0, a.s0 + log_m) of
+// this launch; false = no such kernel.
+template <class F, bool INV, class Fn>
+bool pass_dispatch(bool contig, int log_m, const ErasedArgs &a, Fn &&fn) {
+    constexpr int WB = (int) sizeof(typename F::W);
+    const bool last_pass = a.s0 + log_m == a.n;
+    if (a.lde_beta != 0) {  // first pass of ntt_lde: the fused-expansion twin of this shape (pass.h: lde_dispatch)
+        if constexpr (INV) return false;
+        else return contig && lde_dispatch<F>(log_m, last_pass, fn);
+    }
+    if (!contig)  // 9: 512 rows x one 128-byte segment: N = 2^22 = 13 + 9 in two passes
+        return with_log_m<4, 9>(log_m, [&](auto m) { fn(CfgTag<ColPassCfg<F, decltype(m)::value, INV>>{}); });
+    if (log_m == 13) {
+        fn(CfgTag<ContigCfg13<F, INV>>{});
+        return true;
+    }
+    if (log_m == 14) {
+        if constexpr (WB == 4) fn(CfgTag<ContigCfg14<F, INV>>{});
+        return WB == 4;
+    }
+    // PassDesc::variant 1: a single-pass unit of 2^10 .. 2^12 words on 512 threads x 8 words (radix-8 rounds; 8-byte forward: the
+    // LDS-DMA kernel that otherwise runs as the first pass of a two-pass plan) instead of 256 x 16 -- twice the waves for the same
+    // work, for launches too small to fill the SIMDs (plan.h: plan_alternatives).  Both layouts (pass.h: elem_off / lane_eff);
+    // a fused pointwise operand keeps the default kernel.
+    if (a.variant == 1 && a.in2 == nullptr && with_log_m<10, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfgE8<F, decltype(m)::value, INV>>{}); }))
+        return true;
+    if constexpr (WB == 8) {
+        if (contig_log_e(log_m, WB, last_pass) == 3) {
+            if constexpr (!INV) {  // fused pointwise product: the twins without LDS-DMA
+                if (a.in2 != nullptr) return with_log_m<7, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfgE8<F, decltype(m)::value, INV, false>>{}); });
+            }
+            return with_log_m<7, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfgE8<F, decltype(m)::value, INV>>{}); });
+        }
+    }
+    return with_log_m<1, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfg<F, decltype(m)::value, INV>>{}); });
+}
+
+template <class Cfg>
+PassGeom pass_geometry_of(const ErasedArgs &e) {
+    return pass_geometry(e.n, e.s0, Cfg::LOG_M, Cfg::LOG_C, Cfg::LOG_U, Cfg::CONTIG, e.batch, e.target_wgs, Cfg::PPW_CAP);
+}
+
+// The kernel's argument block for this launch and geometry; false = the launch is refused.  a.tw_sc is set exactly when
+// the scaled-inverse specialisation (N^-1 folded into stage 0, pass.h: fold_scale) is the kernel to run.
+template <class Cfg>
+bool fill_pass_args(const ErasedArgs &e, const PassGeom &g, PassArgs<Cfg> &a) {
+    using W = typename Cfg::W;
+    a = PassArgs<Cfg>{};
+    a.in = (const W *) e.in;
+    a.out = (W *) e.out;
+    a.tw = (const W *) e.tw;
+    a.field = make_field<typename Cfg::F>(e.field);
+    a.n = e.n;
+    a.s0 = e.s0;
+    a.batch = e.batch;
+    a.ppw = g.ppw;
+    a.tp = g.tp;
+    a.log_ul = g.log_ul;
+    a.log_uh = g.log_uh;
+    a.log_up = g.log_up;
+    a.layout = e.layout;
+    a.do_scale = e.do_scale;
+    a.scale = (W) e.scale;
+    a.dbg = e.dbg;
+    a.pg_stride = 1;
+    a.in2 = (const W *) e.in2;
+    a.pw_scale = (W) e.pw_scale;
+    a.skip_if = (const uint32_t *) e.skip_if;
+    // the fused expansion runs in its own kernels and nowhere else (never beside LDS-DMA or the register prefetch: PassCfg::LDE)
+    if ((e.lde_beta != 0) != Cfg::LDE) return false;
+    if constexpr (Cfg::LDE) {
+        if (e.lde_beta < 1 || e.lde_beta > 4 || e.lde_beta >= e.n || e.s0 != 0 || !e.lde_in || !e.lde_s || e.in2) return false;
+        a.lde_in = (const W *) e.lde_in;
+        a.lde_s = (const W *) e.lde_s;
+        a.lde_beta = e.lde_beta;
+    }
+    if constexpr (fold_scale<Cfg>()) {
+        if (e.do_scale && e.tw_sc == nullptr) return false;  // these kernels have no scaling sweep
+        if (e.do_scale) a.tw_sc = (const W *) e.tw_sc;        // N^-1 rides on stage 0
+    }
+#if defined(NTT_PHASE_STAMPS)
+    a.stamps = (unsigned long long *) e.stamps;
+    a.stamp_records = e.stamp_records;
+#endif
+    return true;
+}
+
+// ---- the fused middle pass of the negacyclic product (pass.h: run_product_pass) ------------------------------------
+// fn(CfgTag<PC>{}), PC = ProductCfg / ProductCfgM32 of the unit size: every size with a kernel.  8-byte words 2^7 .. 2^12;
+// 4-byte words 2^5 .. 2^13
+template <class F, class Fn>
+bool product_dispatch(int log_m, Fn &&fn) {
+    if constexpr (sizeof(typename F::W) == 4) return with_log_m<5, 13>(log_m, [&](auto m) { fn(CfgTag<ProductCfgM32<decltype(m)::value>>{}); });
+    else return with_log_m<7, 12>(log_m, [&](auto m) { fn(CfgTag<ProductCfg<decltype(m)::value, F>>{}); });
+}
+// ... and the sizes ntt_polymul_negacyclic takes it at.  (The 4-byte 2^5 unit has a kernel, which the host-model test runs, but
+// its register loads and stores move 8 bytes per polynomial at a time: 3.9 ms per GiB of operands against 1.4 ms for the three
+// separate launches, whose small units are staged through LDS -- tools/polymul_small.py)
+inline bool product_mid_used(const FieldParams &fp, int log_m) { return fp.kind == FK_M32 ? log_m >= 6 && log_m <= 13 : log_m >= 7 && log_m <= 12; }
+
+template <class PC>
+PassGeom product_geometry(int n, uint32_t batch, uint32_t target_wgs) {
+    return pass_geometry(n, 0, PC::CI::LOG_M, 0, PC::CI::LOG_U, true, batch, target_wgs);
+}
+// does the product launch of this unit size cover `batch` polynomials in one grid (blockIdx.y <= 65535)?  The SAME geometry call
+// the launcher makes -- the pre-check of ntt_polymul_negacyclic goes through here, so the two cannot disagree
+inline bool product_mid_fits(const FieldParams &fp, int log_m, int n, uint32_t batch, uint32_t target_wgs) {
+    return with_field(fp, [&](auto f) {
+        bool fits = false;
+        product_dispatch<decltype(f)>(log_m, [&](auto tag) { fits = product_geometry<typename decltype(tag)::Cfg>(n, batch, target_wgs).grid_y <= 65535u; });
+        return fits;
+    });
+}
+
+// one leg of the product launch: the inverse pass of an operand (in, no out) or the forward pass of the product (out, no in)
+template <class Cfg>
+PassArgs<Cfg> product_leg(const ErasedArgs &e, const PassGeom &g, const void *in, void *out, const void *tw, int layout) {
+    using W = typename Cfg::W;
+    PassArgs<Cfg> a{};
+    a.in = (const W *) in;
+    a.out = (W *) out;
+    a.tw = (const W *) tw;
+    a.field = make_field<typename Cfg::F>(e.field);
+    a.n = e.n;
+    a.batch = e.batch;
+    a.ppw = g.ppw;
+    a.tp = g.tp;
+    a.log_ul = g.log_ul;
+    a.log_uh = g.log_uh;
+    a.log_up = g.log_up;
+    a.layout = layout;
+    a.pg_stride = 1;
+    return a;
+}
+// aa: inverse leg of operand e.in (operand e.in2: the same block with that `in`); af: forward leg, product * pw_scale -> e.out
+template <class PC>
+void fill_product_args(const ErasedArgs &e, const PassGeom &g, PassArgs<typename PC::CI> &aa, PassArgs<typename PC::CF> &af) {
+    aa = product_leg<typename PC::CI>(e, g, e.in, nullptr, e.tw, LAYOUT_NATURAL);
+    af = product_leg<typename PC::CF>(e, g, nullptr, e.out, e.tw2, e.layout);
+    af.pw_scale = (typename PC::CF::W) e.pw_scale;
+}
+
+}  // namespace ntt

@@ -208,95 +208,69 @@ inline unsigned grid_for(size_t work) {
 
 }  // namespace
 
-hipError_t launch_pointwise_gl(const void *a, const void *b, void *c, size_t count, uint64_t scale,
-                               hipStream_t s) {
+// by field: the launchers of the pass / product translation units
+hipError_t launch_pass(bool inverse, bool contig, int log_m, const ErasedArgs &a, hipStream_t s) {
+    return with_field(a.field, [&](auto f) {
+        using F = decltype(f);
+        return inverse ? launch_pass_of<F, true>(contig, log_m, a, s) : launch_pass_of<F, false>(contig, log_m, a, s);
+    });
+}
+
+hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s) {
+    return with_field(a.field, [&](auto f) { return launch_product_mid_of<decltype(f)>(log_m, a, s); });
+}
+
+hipError_t launch_pointwise(const FieldParams &fp, const void *a, const void *b, void *c, size_t count, uint64_t scale, hipStream_t s) {
     if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(pointwise_kernel<FieldGL>, dim3(grid_for(count / 2)), dim3(256), 0, s,
-                       (const uint64_t *) a, (const uint64_t *) b, (uint64_t *) c, count, FieldGL{}, scale,
-                       scale != 1 ? 1 : 0);
-    return hipGetLastError();
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        using W = typename F::W;
+        hipLaunchKernelGGL(pointwise_kernel<F>, dim3(grid_for(count / (16 / sizeof(W)))), dim3(256), 0, s, (const W *) a, (const W *) b, (W *) c, count, f,
+                           (W) scale, scale != 1 ? 1 : 0);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_pointwise_m32(const void *a, const void *b, void *c, size_t count, uint32_t p,
-                                uint32_t pinv, uint32_t r2, uint32_t scale, hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(pointwise_kernel<FieldM32>, dim3(grid_for(count / 4)), dim3(256), 0, s,
-                       (const uint32_t *) a, (const uint32_t *) b, (uint32_t *) c, count,
-                       FieldM32{p, pinv, r2}, scale, scale != 1 ? 1 : 0);
-    return hipGetLastError();
+hipError_t launch_gen_table(const FieldParams &fp, void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, hipStream_t s) {
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        using W = typename F::W;
+        hipLaunchKernelGGL(gen_table_kernel<F>, dim3(grid_for((size_t) 1 << logn)), dim3(256), 0, s, (W *) T, logn, kind, (W) base_m, (W) one_m, f);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_pointwise_m64(const void *a, const void *b, void *c, size_t count, uint64_t p,
-                                uint64_t pinv, uint64_t r2, uint64_t scale, hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(pointwise_kernel<FieldM64>, dim3(grid_for(count / 2)), dim3(256), 0, s,
-                       (const uint64_t *) a, (const uint64_t *) b, (uint64_t *) c, count,
-                       FieldM64{p, pinv, r2}, scale, scale != 1 ? 1 : 0);
-    return hipGetLastError();
+hipError_t launch_gen_coset(const FieldParams &fp, void *s_out, int logn, uint32_t len, uint64_t shift_m, uint64_t one_m, hipStream_t s) {
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        using W = typename F::W;
+        hipLaunchKernelGGL(gen_coset_kernel<F>, dim3(grid_for(len)), dim3(256), 0, s, (W *) s_out, logn, len, (W) shift_m, (W) one_m, f);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_gen_table_gl(void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, hipStream_t s) {
-    hipLaunchKernelGGL(gen_table_kernel<FieldGL>, dim3(grid_for((size_t) 1 << logn)), dim3(256), 0, s,
-                       (uint64_t *) T, logn, kind, base_m, one_m, FieldGL{});
-    return hipGetLastError();
-}
-
-hipError_t launch_gen_table_m32(void *T, int logn, int kind, uint32_t base_m, uint32_t one_m, uint32_t p,
-                                uint32_t pinv, uint32_t r2, hipStream_t s) {
-    hipLaunchKernelGGL(gen_table_kernel<FieldM32>, dim3(grid_for((size_t) 1 << logn)), dim3(256), 0, s,
-                       (uint32_t *) T, logn, kind, base_m, one_m, FieldM32{p, pinv, r2});
-    return hipGetLastError();
-}
-
-hipError_t launch_gen_table_m64(void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, uint64_t p,
-                                uint64_t pinv, uint64_t r2, hipStream_t s) {
-    hipLaunchKernelGGL(gen_table_kernel<FieldM64>, dim3(grid_for((size_t) 1 << logn)), dim3(256), 0, s,
-                       (uint64_t *) T, logn, kind, base_m, one_m, FieldM64{p, pinv, r2});
-    return hipGetLastError();
-}
-
-hipError_t launch_gen_coset(int fk, void *s_out, int logn, uint32_t len, uint64_t shift_m, uint64_t one_m, const ErasedArgs &e, hipStream_t s) {
-    const dim3 grid(grid_for(len)), block(256);
-    if (fk == 1)
-        hipLaunchKernelGGL(gen_coset_kernel<FieldGL>, grid, block, 0, s, (uint64_t *) s_out, logn, len, shift_m, one_m, FieldGL{});
-    else if (fk == 2)
-        hipLaunchKernelGGL(gen_coset_kernel<FieldM64>, grid, block, 0, s, (uint64_t *) s_out, logn, len, shift_m, one_m,
-                           FieldM64{e.p64, e.pinv64, e.r2_64});
-    else
-        hipLaunchKernelGGL(gen_coset_kernel<FieldM32>, grid, block, 0, s, (uint32_t *) s_out, logn, len, (uint32_t) shift_m, (uint32_t) one_m,
-                           FieldM32{e.p, e.pinv, e.r2});
-    return hipGetLastError();
-}
-
-hipError_t launch_lde_expand(int fk, const void *in, const void *s_vec, void *out, int n, int beta, size_t batch, const ErasedArgs &e, hipStream_t s) {
-    const size_t chunks = ((batch << n) * (fk == 0 ? 4 : 8)) / 16;  // 2^n words >= 16 bytes (n >= 2)
+hipError_t launch_lde_expand(const FieldParams &fp, const void *in, const void *s_vec, void *out, int n, int beta, size_t batch, hipStream_t s) {
+    const size_t chunks = ((batch << n) * (size_t) field_word_bytes(fp)) / 16;  // 2^n words >= 16 bytes (n >= 2)
     if (chunks == 0) return hipSuccess;
-    const dim3 grid(grid_for(chunks)), block(256);
-    if (fk == 1)
-        hipLaunchKernelGGL(lde_expand_kernel<FieldGL>, grid, block, 0, s, (const uint64_t *) in, (const uint64_t *) s_vec, (uint64_t *) out, chunks, n,
-                           beta, FieldGL{});
-    else if (fk == 2)
-        hipLaunchKernelGGL(lde_expand_kernel<FieldM64>, grid, block, 0, s, (const uint64_t *) in, (const uint64_t *) s_vec, (uint64_t *) out, chunks, n,
-                           beta, FieldM64{e.p64, e.pinv64, e.r2_64});
-    else
-        hipLaunchKernelGGL(lde_expand_kernel<FieldM32>, grid, block, 0, s, (const uint32_t *) in, (const uint32_t *) s_vec, (uint32_t *) out, chunks, n,
-                           beta, FieldM32{e.p, e.pinv, e.r2});
-    return hipGetLastError();
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        using W = typename F::W;
+        hipLaunchKernelGGL(lde_expand_kernel<F>, dim3(grid_for(chunks)), dim3(256), 0, s, (const W *) in, (const W *) s_vec, (W *) out, chunks, n, beta, f);
+        return hipGetLastError();
+    });
 }
 
-hipError_t launch_scale_table_gl(const void *T, void *out, size_t count, uint64_t c_m, hipStream_t s) {
+hipError_t launch_scale_table(const FieldParams &fp, const void *T, void *out, size_t count, uint64_t c_m, hipStream_t s) {
     if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(scale_table_kernel<FieldGL>, dim3(grid_for(count)), dim3(256), 0, s, (const uint64_t *) T,
-                       (uint64_t *) out, count, c_m, FieldGL{});
-    return hipGetLastError();
-}
-
-hipError_t launch_scale_table_m64(const void *T, void *out, size_t count, uint64_t c_m, uint64_t p, uint64_t pinv, uint64_t r2,
-                                  hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(scale_table_kernel<FieldM64>, dim3(grid_for(count)), dim3(256), 0, s, (const uint64_t *) T,
-                       (uint64_t *) out, count, c_m, FieldM64{p, pinv, r2});
-    return hipGetLastError();
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        if constexpr (sizeof(typename F::W) == 8) {
+            hipLaunchKernelGGL(scale_table_kernel<F>, dim3(grid_for(count)), dim3(256), 0, s, (const uint64_t *) T, (uint64_t *) out, count, c_m, f);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;  // 4-byte words keep the scaling sweep (pass.h: fold_scale): no such table
+        }
+    });
 }
 
 hipError_t launch_count_noncanonical(const void *a, size_t count, int word_bytes, uint64_t p, void *d_out, hipStream_t s) {
@@ -309,30 +283,15 @@ hipError_t launch_count_noncanonical(const void *a, size_t count, int word_bytes
     return hipGetLastError();
 }
 
-hipError_t launch_stage_gl(void *data, const void *tw, int n, int stage, size_t batch, hipStream_t s) {
+hipError_t launch_stage(const FieldParams &fp, void *data, const void *tw, int n, int stage, size_t batch, hipStream_t s) {
     const size_t total = batch << (n - 1);
     if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(stage_kernel<FieldGL>, dim3(grid_for(total)), dim3(256), 0, s, (uint64_t *) data,
-                       (const uint64_t *) tw, n, stage, total, FieldGL{});
-    return hipGetLastError();
-}
-
-hipError_t launch_stage_m32(void *data, const void *tw, int n, int stage, size_t batch, uint32_t p,
-                            uint32_t pinv, uint32_t r2, hipStream_t s) {
-    const size_t total = batch << (n - 1);
-    if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(stage_kernel<FieldM32>, dim3(grid_for(total)), dim3(256), 0, s, (uint32_t *) data,
-                       (const uint32_t *) tw, n, stage, total, FieldM32{p, pinv, r2});
-    return hipGetLastError();
-}
-
-hipError_t launch_stage_m64(void *data, const void *tw, int n, int stage, size_t batch, uint64_t p,
-                            uint64_t pinv, uint64_t r2, hipStream_t s) {
-    const size_t total = batch << (n - 1);
-    if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(stage_kernel<FieldM64>, dim3(grid_for(total)), dim3(256), 0, s, (uint64_t *) data,
-                       (const uint64_t *) tw, n, stage, total, FieldM64{p, pinv, r2});
-    return hipGetLastError();
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        using W = typename F::W;
+        hipLaunchKernelGGL(stage_kernel<F>, dim3(grid_for(total)), dim3(256), 0, s, (W *) data, (const W *) tw, n, stage, total, f);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace ntt

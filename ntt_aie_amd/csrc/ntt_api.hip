@@ -78,47 +78,42 @@ struct RoctxRange {
 }  // namespace
 
 struct ntt_plan {
-    int logn;
-    uint64_t p;
-    int word_bytes;
-    int device;
-    int fk;  // arithmetic: FK_M32 (4-byte words), FK_GL (p = 2^64 - 2^32 + 1), FK_M64 (any other odd 8-byte modulus)
-    // FieldM32 parameters
-    uint32_t pinv, r2;
-    // FieldM64 parameters
-    uint64_t pinv64, r2_64;
+    int logn = 0;
+    uint64_t p = 0;
+    int word_bytes = 0;
+    int device = 0;
+    ntt::FieldParams field = {};  // arithmetic (launch.h: FieldKind) and its Montgomery constants
     // device tables, table form
-    void *d_tw_fwd;
-    void *d_tw_inv;
-    void *d_tw_inv_sc;  // 8-byte words (both fields): T^-1[N/2 + i] * N^-1, i < N/2 (stage-0 twiddles of the scaled inverse, pass.h: fold_scale)
-    bool has_table, has_inv;
-    uint64_t scale_tf;     // N^-1 in table form
-    uint64_t ninv_plain;   // N^-1 plain
-    uint32_t target_wgs;      // workgroups per launch the batch loop of a CONTIG pass is sized for
-    uint32_t target_wgs_col;  // ... of a column pass (shorter loops win there)
-    int dbg;            // experiment build only (NTT_DEBUG_FLAGS); always 0 in the product
-    int force_variant;  // experiment build only (NTT_PASS_VARIANT=k): every CONTIG pass runs kernel variant k; -1 in the product
-    int only_pass;      // experiment build only (NTT_ONLY_PASS=k): ntt_forward launches pass k alone (power / clock of one kernel); -1 in the product
-    int fused;          // experiment build only (NTT_FUSED=1): N = 2^16 Goldilocks forward through the XCD-local fused launch
-    void *d_fused_ctl;  // counters of the fused launch (plan-owned; null in the product)
-    size_t fused_max_batch;
-    unsigned long long *d_counter;  // one device word for ntt_count_noncanonical (no allocation per call)
-    std::mutex counter_mu;          // ... which is the only entry point that writes plan-owned state after creation
+    void *d_tw_fwd = nullptr;
+    void *d_tw_inv = nullptr;
+    void *d_tw_inv_sc = nullptr;  // 8-byte words (both fields): T^-1[N/2 + i] * N^-1, i < N/2 (stage-0 twiddles of the scaled inverse, pass.h: fold_scale)
+    bool has_table = false, has_inv = false;
+    uint64_t scale_tf = 0;     // N^-1 in table form
+    uint64_t ninv_plain = 0;   // N^-1 plain
+    uint32_t target_wgs = 8192;  // workgroups per launch the batch loop of a CONTIG pass is sized for (sweep: profiles/)
+    // ... of a column pass: 16384 (their tile streams 8 polynomials per workgroup at N = 2^16, batch 4096, instead of 16): -4 %
+    uint32_t target_wgs_col = 2 * 8192;
+    int dbg = 0;             // experiment build only (NTT_DEBUG_FLAGS); always 0 in the product
+    int force_variant = -1;  // experiment build only (NTT_PASS_VARIANT=k): every CONTIG pass runs kernel variant k; -1 in the product
+    int only_pass = -1;      // experiment build only (NTT_ONLY_PASS=k): a forward run of passes launches pass k alone (power / clock of one kernel); -1 in the product
+    int fused = 0;           // experiment build only (NTT_FUSED=1): N = 2^16 Goldilocks forward through the XCD-local fused launch
+    void *d_fused_ctl = nullptr;  // counters of the fused launch (plan-owned; null in the product)
+    size_t fused_max_batch = 0;
+    unsigned long long *d_counter = nullptr;  // one device word for ntt_count_noncanonical (no allocation per call)
+    std::mutex counter_mu;                    // ... which is the only entry point that writes plan-owned state after creation
     std::vector<PassDesc> passes;  // = alts[0].passes: the default decomposition (ntt_plan_info 3 / 32+ / 64+)
     std::vector<PlanAlt> alts;     // launch-time alternatives, ascending min_batch (plan.h: plan_alternatives)
-    int forced_alt;                // ntt_plan_set_policy: -1 = by batch, k >= 0 = always alternative k
+    int forced_alt = -1;           // ntt_plan_set_policy: -1 = by batch, k >= 0 = always alternative k
     // ntt_plan_set_coset: low-degree extension onto shift * <w_N> from N >> lde_beta coefficients (0 = not set)
-    int lde_beta;
-    uint64_t lde_shift;
-    void *d_lde_s;      // s[i] = shift^bitrev(i), table form, max(N >> lde_beta, 4) words (misc_kernels.hip: gen_coset_kernel)
-    int lde_unfused;    // experiment build only (NTT_LDE_UNFUSED=1): ntt_lde takes the separate expansion kernel at every size; 0 in the product
+    int lde_beta = 0;
+    uint64_t lde_shift = 0;
+    void *d_lde_s = nullptr;  // s[i] = shift^bitrev(i), table form, max(N >> lde_beta, 4) words (misc_kernels.hip: gen_coset_kernel)
+    int lde_unfused = 0;      // experiment build only (NTT_LDE_UNFUSED=1): ntt_lde takes the separate expansion kernel at every size; 0 in the product
 };
 
 static_assert(NTT_E_NOMEM == NTT_E_NOMEM_GUARD && NTT_E_INTERNAL == NTT_E_INTERNAL_GUARD, "guard.h codes = include/ntt_hip.h codes");
 
 namespace {
-
-enum { FK_M32 = 0, FK_GL = 1, FK_M64 = 2 };
 
 // frees what a (possibly half-built) plan owns; the device must be current
 void free_plan(ntt_plan *pl) {
@@ -141,17 +136,6 @@ struct PlanDeleter {
     }
 };
 using PlanHolder = std::unique_ptr<ntt_plan, PlanDeleter>;
-
-hipError_t launch_fwd(const ntt_plan *pl, const PassDesc &pd, const ntt::ErasedArgs &a, hipStream_t s) {
-    return pl->fk == FK_GL ? ntt::launch_gl_fwd(pd.contig, pd.log_m, a, s)
-         : pl->fk == FK_M64 ? ntt::launch_m64_fwd(pd.contig, pd.log_m, a, s)
-                            : ntt::launch_m32_fwd(pd.contig, pd.log_m, a, s);
-}
-hipError_t launch_inv(const ntt_plan *pl, const PassDesc &pd, const ntt::ErasedArgs &a, hipStream_t s) {
-    return pl->fk == FK_GL ? ntt::launch_gl_inv(pd.contig, pd.log_m, a, s)
-         : pl->fk == FK_M64 ? ntt::launch_m64_inv(pd.contig, pd.log_m, a, s)
-                            : ntt::launch_m32_inv(pd.contig, pd.log_m, a, s);
-}
 
 size_t table_bytes(const ntt_plan *pl) { return ((size_t) 1 << pl->logn) * pl->word_bytes; }
 size_t sc_table_bytes(const ntt_plan *pl) { return pl->word_bytes == 8 ? table_bytes(pl) / 2 : 0; }
@@ -179,12 +163,7 @@ ntt::ErasedArgs base_args(const ntt_plan *pl, const PassDesc &pd, const void *in
     memset(&a, 0, sizeof(a));
     a.in = in;
     a.out = out;
-    a.p = (uint32_t) pl->p;
-    a.pinv = pl->pinv;
-    a.r2 = pl->r2;
-    a.p64 = pl->p;
-    a.pinv64 = pl->pinv64;
-    a.r2_64 = pl->r2_64;
+    a.field = pl->field;
     a.n = pl->logn;
     a.s0 = pd.s0;
     a.batch = (uint32_t) batch;
@@ -213,13 +192,54 @@ int check_io(const ntt_plan *pl, const void *a, const void *b, size_t batch) {
     return NTT_OK;
 }
 
+int check_layout(const ntt_plan *pl, int layout) {
+    if (layout != NTT_LAYOUT_NATURAL && layout != NTT_LAYOUT_AIE_BLOCK16) return NTT_E_ARG;
+    if (layout == NTT_LAYOUT_AIE_BLOCK16 && pl->logn < 4) return NTT_E_LAYOUT;
+    return NTT_OK;
+}
+
+// PassArgs::pw_scale of a fused pointwise product * scale (plain): scale * R^2, i.e. the table form of the table form
+uint64_t pw_scale_form(const ntt_plan *pl, uint64_t scale_plain) {
+    return to_table_form(to_table_form(scale_plain % pl->p, pl->p, pl->word_bytes), pl->p, pl->word_bytes);
+}
+
+// One pass launch: the arguments every launch of this plan shares, the table of the direction, the ROCTX range;
+// tweak(a) adds what only this launch has.
+template <class Tweak>
+hipError_t launch_one(const ntt_plan *pl, const PassDesc &pd, bool inverse, const char *what, const void *in, void *out, size_t batch,
+                      int layout, hipStream_t s, Tweak &&tweak) {
+    RoctxRange pass(what, pd.contig, pd.s0, pd.log_m);
+    ntt::ErasedArgs a = base_args(pl, pd, in, out, batch);
+    a.tw = inverse ? pl->d_tw_inv : pl->d_tw_fwd;
+    a.layout = layout;
+    tweak(a);
+    return ntt::launch_pass(inverse, pd.contig, pd.log_m, a, s);
+}
+
+// Passes [lo, hi) of a decomposition in execution order (forward: ascending, inverse: descending): the first one launched
+// reads `in`, the others run in place on `out` (which may alias `in`).  tweak(a, i) sees the arguments of pass i.
+template <class Tweak>
+int run_passes(const ntt_plan *pl, const std::vector<PassDesc> &passes, size_t lo, size_t hi, bool inverse, const char *what,
+               const void *in, void *out, size_t batch, int layout, hipStream_t s, Tweak &&tweak) {
+    const void *src = in;
+    for (size_t k = lo; k < hi; k++) {
+        const size_t i = inverse ? lo + (hi - 1 - k) : k;
+#if defined(NTT_EXPERIMENT)
+        if (!inverse && pl->only_pass >= 0 && (int) i != pl->only_pass) continue;  // timing experiment: outputs meaningless
+#endif
+        const hipError_t e = launch_one(pl, passes[i], inverse, what, src, out, batch, layout, s, [&](ntt::ErasedArgs &a) { tweak(a, i); });
+        if (e != hipSuccess) return (int) e;
+        src = out;
+    }
+    return NTT_OK;
+}
+
 // in2 != null: transform in[j] * in2[j] * pw_scale (plain) instead of in[j]; the product is folded into
 // the load of the first pass
 // `forced`: the decomposition to run (a product picks ONE for all of its transforms); null = passes_for(batch)
 int run_forward(ntt_plan *pl, const void *d_in, void *d_out, size_t batch, int layout, hipStream_t s,
                 const void *in2 = nullptr, uint64_t pw_scale_plain = 1, const std::vector<PassDesc> *forced = nullptr) {
     RoctxRange whole(in2 ? "ntt_forward(product)" : "ntt_forward");
-    const void *src = d_in;
     const void *skip_if = nullptr;
 #if defined(NTT_EXPERIMENT)
     if (pl->d_fused_ctl && !in2 && d_in != d_out && layout == NTT_LAYOUT_NATURAL && batch >= 64 && batch % 8 == 0 &&
@@ -233,46 +253,33 @@ int run_forward(ntt_plan *pl, const void *d_in, void *d_out, size_t batch, int l
     }
 #endif
     const std::vector<PassDesc> &passes = forced ? *forced : passes_for(pl, batch);
-    for (const PassDesc &pd : passes) {
-#if defined(NTT_EXPERIMENT)
-        if (pl->only_pass >= 0 && (int) (&pd - &passes.front()) != pl->only_pass) continue;  // timing experiment: outputs meaningless
-#endif
-        RoctxRange pass("fwd pass", pd.contig, pd.s0, pd.log_m);
-        ntt::ErasedArgs a = base_args(pl, pd, src, d_out, batch);
+    const uint64_t pw_scale = in2 ? pw_scale_form(pl, pw_scale_plain) : 0;
+    return run_passes(pl, passes, 0, passes.size(), false, "fwd pass", d_in, d_out, batch, layout, s, [&](ntt::ErasedArgs &a, size_t i) {
         a.skip_if = skip_if;
-        if (&pd == &passes.front() && in2) {  // first pass only (d_out may alias d_in)
+        if (i == 0 && in2) {  // first pass only (d_out may alias d_in)
             a.in2 = in2;
-            a.pw_scale = to_table_form(to_table_form(pw_scale_plain % pl->p, pl->p, pl->word_bytes), pl->p, pl->word_bytes);
+            a.pw_scale = pw_scale;
         }
-        a.tw = pl->d_tw_fwd;
-        a.layout = layout;
-        hipError_t e = launch_fwd(pl, pd, a, s);
-        if (e != hipSuccess) return (int) e;
-        src = d_out;
-    }
-    return NTT_OK;
+    });
 }
 
 int run_inverse(ntt_plan *pl, const void *d_in, void *d_out, size_t batch, int layout, int scale,
                 hipStream_t s, const std::vector<PassDesc> *forced = nullptr) {
     RoctxRange whole("ntt_inverse");
-    const void *src = d_in;
     const std::vector<PassDesc> &passes = forced ? *forced : passes_for(pl, batch);
-    for (size_t i = passes.size(); i-- > 0;) {
-        const PassDesc &pd = passes[i];
-        RoctxRange pass("inv pass", pd.contig, pd.s0, pd.log_m);
-        ntt::ErasedArgs a = base_args(pl, pd, src, d_out, batch);
-        a.tw = pl->d_tw_inv;
-        a.layout = layout;
+    return run_passes(pl, passes, 0, passes.size(), true, "inv pass", d_in, d_out, batch, layout, s, [&](ntt::ErasedArgs &a, size_t i) {
         a.do_scale = (scale && i == 0) ? 1 : 0;
         a.scale = pl->scale_tf;
         // 8-byte words: N^-1 rides on the last executed stage (stage 0 of the CONTIG pass) instead of a sweep over the outputs
         a.tw_sc = a.do_scale ? pl->d_tw_inv_sc : nullptr;
-        hipError_t e = launch_inv(pl, pd, a, s);
-        if (e != hipSuccess) return (int) e;
-        src = d_out;
-    }
-    return NTT_OK;
+    });
+}
+
+// device-to-device, no host copy: over xGMI when the devices differ (hipMemcpyPeer), which is what the
+// reference's on-chip table broadcast does below its host (src/aie2.py:96-104)
+hipError_t copy_d2d(void *dst, int dst_dev, const void *from, int from_dev, size_t bytes) {
+    if (bytes == 0 || !dst || !from) return hipSuccess;
+    return dst_dev == from_dev ? hipMemcpy(dst, from, bytes, hipMemcpyDeviceToDevice) : hipMemcpyPeer(dst, dst_dev, from, from_dev, bytes);
 }
 
 }  // namespace
@@ -340,41 +347,15 @@ int ntt_plan_create(ntt_plan_t *out, int logn, uint64_t p, int word_bytes, int d
     PlanHolder holder(new (std::nothrow) ntt_plan());
     ntt_plan *pl = holder.get();
     if (!pl) return NTT_E_NOMEM;
-    pl->d_tw_fwd = pl->d_tw_inv = pl->d_tw_inv_sc = nullptr;
-    pl->d_fused_ctl = nullptr;
-    pl->d_counter = nullptr;
-    pl->d_lde_s = nullptr;
-    pl->lde_beta = 0;
-    pl->lde_shift = 0;
-    pl->lde_unfused = 0;
     pl->device = device;
     pl->logn = logn;
     pl->p = p;
     pl->word_bytes = word_bytes;
-    pl->has_table = pl->has_inv = false;
-    pl->pinv = pl->r2 = 0;
-    pl->pinv64 = pl->r2_64 = 0;
-    pl->fk = word_bytes == 4 ? FK_M32 : (p == GOLDILOCKS ? FK_GL : FK_M64);
-    if (pl->fk == FK_M32) {
-        pl->pinv = mont_pinv((uint32_t) p);
-        pl->r2 = mont_r2((uint32_t) p);
-    } else if (pl->fk == FK_M64) {
-        pl->pinv64 = mont_pinv64(p);
-        pl->r2_64 = mont_r2_64(p);
-    }
+    pl->field = ntt::field_params(word_bytes, p);
     pl->ninv_plain = powmod(p / 2 + 1, (uint64_t) logn, p);  // (2^-1)^logn; 2^-1 = (p + 1) / 2 = p / 2 + 1 for odd p (no overflow at p near 2^64)
     pl->scale_tf = to_table_form(pl->ninv_plain, p, word_bytes);
-    pl->target_wgs = 8192;  // workgroups per launch the batch loop is sized for (sweep: profiles/)
-    // column passes: 16384 (their tile streams 8 polynomials per workgroup at N = 2^16, batch 4096, instead of 16): -4 %
-    pl->target_wgs_col = 2 * pl->target_wgs;
-    pl->dbg = 0;
-    pl->only_pass = -1;
-    pl->force_variant = -1;
-    pl->fused = 0;
-    pl->fused_max_batch = 0;
     pl->alts = plan_alternatives(logn, word_bytes, p);
     pl->passes = pl->alts[0].passes;
-    pl->forced_alt = -1;
 #if defined(NTT_EXPERIMENT)
     // Experiment knobs exist only in libntt_hip_exp.so (make exp; tools/): the product library reads NO environment
     // variable, so a stray NTT_DEBUG_FLAGS in a user's shell cannot redirect loads and stores.
@@ -504,27 +485,10 @@ int ntt_plan_generate_twiddles(ntt_plan_t pl, int kind, uint64_t g) NTT_GUARD {
     const uint64_t one_m = to_table_form(1 % p, p, wb);
     DeviceGuard g_(pl->device);
     if (g_.err != hipSuccess) return (int) g_.err;
-    hipError_t e;
-    if (pl->fk == FK_M64) {
-        e = ntt::launch_gen_table_m64(pl->d_tw_fwd, pl->logn, kind, to_table_form(base, p, 8), one_m, p, pl->pinv64, pl->r2_64, nullptr);
-        if (e == hipSuccess)
-            e = ntt::launch_gen_table_m64(pl->d_tw_inv, pl->logn, kind, to_table_form(base_inv, p, 8), one_m, p, pl->pinv64, pl->r2_64, nullptr);
-        if (e == hipSuccess)
-            e = ntt::launch_scale_table_m64((const uint64_t *) pl->d_tw_inv + N / 2, pl->d_tw_inv_sc, N / 2, pl->scale_tf, p, pl->pinv64,
-                                            pl->r2_64, nullptr);
-    } else if (wb == 8) {
-        e = ntt::launch_gen_table_gl(pl->d_tw_fwd, pl->logn, kind, to_table_form(base, p, 8), one_m, nullptr);
-        if (e == hipSuccess)
-            e = ntt::launch_gen_table_gl(pl->d_tw_inv, pl->logn, kind, to_table_form(base_inv, p, 8), one_m, nullptr);
-        if (e == hipSuccess)  // stage-0 twiddles of the scaled inverse: T^-1[N/2 + i] * N^-1
-            e = ntt::launch_scale_table_gl((const uint64_t *) pl->d_tw_inv + N / 2, pl->d_tw_inv_sc, N / 2, pl->scale_tf, nullptr);
-    } else {
-        e = ntt::launch_gen_table_m32(pl->d_tw_fwd, pl->logn, kind, (uint32_t) to_table_form(base, p, 4),
-                                      (uint32_t) one_m, (uint32_t) p, pl->pinv, pl->r2, nullptr);
-        if (e == hipSuccess)
-            e = ntt::launch_gen_table_m32(pl->d_tw_inv, pl->logn, kind, (uint32_t) to_table_form(base_inv, p, 4),
-                                          (uint32_t) one_m, (uint32_t) p, pl->pinv, pl->r2, nullptr);
-    }
+    hipError_t e = ntt::launch_gen_table(pl->field, pl->d_tw_fwd, pl->logn, kind, to_table_form(base, p, wb), one_m, nullptr);
+    if (e == hipSuccess) e = ntt::launch_gen_table(pl->field, pl->d_tw_inv, pl->logn, kind, to_table_form(base_inv, p, wb), one_m, nullptr);
+    if (e == hipSuccess && pl->d_tw_inv_sc)  // 8-byte words: stage-0 twiddles of the scaled inverse, T^-1[N/2 + i] * N^-1
+        e = ntt::launch_scale_table(pl->field, (const uint64_t *) pl->d_tw_inv + N / 2, pl->d_tw_inv_sc, N / 2, pl->scale_tf, nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) return (int) e;
     pl->has_table = true;
@@ -622,9 +586,8 @@ int ntt_plan_set_coset(ntt_plan_t pl, int log_blowup, uint64_t shift) NTT_GUARD 
     void *d_s = nullptr;
     hipError_t e = hipMalloc(&d_s, words * (size_t) pl->word_bytes);
     if (e != hipSuccess) return (int) e;
-    const ntt::ErasedArgs fa = base_args(pl, pl->passes.front(), nullptr, nullptr, 0);  // the field's constants
-    e = ntt::launch_gen_coset(pl->fk, d_s, pl->logn - log_blowup, (uint32_t) words, to_table_form(shift, pl->p, pl->word_bytes),
-                              to_table_form(1 % pl->p, pl->p, pl->word_bytes), fa, nullptr);
+    e = ntt::launch_gen_coset(pl->field, d_s, pl->logn - log_blowup, (uint32_t) words, to_table_form(shift, pl->p, pl->word_bytes),
+                              to_table_form(1 % pl->p, pl->p, pl->word_bytes), nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
         (void) hipFree(d_s);
@@ -652,18 +615,11 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
     pl->target_wgs = src->target_wgs;
     pl->target_wgs_col = src->target_wgs_col;
     if (src->has_table) {
-        // device-to-device, no host copy of the table: over xGMI when the devices differ (hipMemcpyPeer), which is what the
-        // reference's on-chip table broadcast does below its host (src/aie2.py:96-104)
-        auto copy = [&](void *dst, const void *from, size_t bytes) -> hipError_t {
-            if (bytes == 0 || !dst || !from) return hipSuccess;
-            return device == src->device ? hipMemcpy(dst, from, bytes, hipMemcpyDeviceToDevice)
-                                         : hipMemcpyPeer(dst, device, from, src->device, bytes);
-        };
         DeviceGuard g(device);
         hipError_t e = g.err;
-        if (e == hipSuccess) e = copy(pl->d_tw_fwd, src->d_tw_fwd, table_bytes(src));
-        if (e == hipSuccess) e = copy(pl->d_tw_inv, src->d_tw_inv, table_bytes(src));
-        if (e == hipSuccess) e = copy(pl->d_tw_inv_sc, src->d_tw_inv_sc, sc_table_bytes(src));
+        if (e == hipSuccess) e = copy_d2d(pl->d_tw_fwd, device, src->d_tw_fwd, src->device, table_bytes(src));
+        if (e == hipSuccess) e = copy_d2d(pl->d_tw_inv, device, src->d_tw_inv, src->device, table_bytes(src));
+        if (e == hipSuccess) e = copy_d2d(pl->d_tw_inv_sc, device, src->d_tw_inv_sc, src->device, sc_table_bytes(src));
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) {
             (void) ntt_plan_destroy(pl);
@@ -678,9 +634,7 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
         DeviceGuard g(device);
         hipError_t e = g.err;
         if (e == hipSuccess) e = hipMalloc(&pl->d_lde_s, bytes);
-        if (e == hipSuccess)
-            e = device == src->device ? hipMemcpy(pl->d_lde_s, src->d_lde_s, bytes, hipMemcpyDeviceToDevice)
-                                      : hipMemcpyPeer(pl->d_lde_s, device, src->d_lde_s, src->device, bytes);
+        if (e == hipSuccess) e = copy_d2d(pl->d_lde_s, device, src->d_lde_s, src->device, bytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) {
             (void) ntt_plan_destroy(pl);
@@ -697,8 +651,7 @@ int ntt_forward(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int 
     int rc = check_io(pl, d_in, d_out, batch);
     if (rc) return rc;
     if (!pl->has_table) return NTT_E_NOTABLE;
-    if (out_layout != NTT_LAYOUT_NATURAL && out_layout != NTT_LAYOUT_AIE_BLOCK16) return NTT_E_ARG;
-    if (out_layout == NTT_LAYOUT_AIE_BLOCK16 && pl->logn < 4) return NTT_E_LAYOUT;
+    if ((rc = check_layout(pl, out_layout)) != NTT_OK) return rc;
     if (batch == 0) return NTT_OK;
     DeviceGuard g(pl->device);
     if (g.err != hipSuccess) return (int) g.err;
@@ -710,8 +663,7 @@ int ntt_lde(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int out_
     if (rc) return rc;
     if (!pl->has_table) return NTT_E_NOTABLE;
     if (pl->lde_beta == 0) return NTT_E_ARG;
-    if (out_layout != NTT_LAYOUT_NATURAL && out_layout != NTT_LAYOUT_AIE_BLOCK16) return NTT_E_ARG;
-    if (out_layout == NTT_LAYOUT_AIE_BLOCK16 && pl->logn < 4) return NTT_E_LAYOUT;
+    if ((rc = check_layout(pl, out_layout)) != NTT_OK) return rc;
     if (batch == 0) return NTT_OK;
     const int beta = pl->lde_beta;
     const uintptr_t in0 = (uintptr_t) d_in, in1 = in0 + ((batch << (pl->logn - beta)) * (size_t) pl->word_bytes);
@@ -724,28 +676,17 @@ int ntt_lde(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int out_
     const std::vector<PassDesc> &passes = passes_for(pl, batch);
     if (!lde_fused(pl)) {
         // expansion as a launch of its own, then the ordinary transform in place
-        const ntt::ErasedArgs fa = base_args(pl, passes.front(), nullptr, nullptr, 0);
-        hipError_t e = ntt::launch_lde_expand(pl->fk, d_in, pl->d_lde_s, d_out, pl->logn, beta, batch, fa, s);
+        hipError_t e = ntt::launch_lde_expand(pl->field, d_in, pl->d_lde_s, d_out, pl->logn, beta, batch, s);
         if (e != hipSuccess) return (int) e;
         return run_forward(pl, d_out, d_out, batch, out_layout, s, nullptr, 1, &passes);
     }
-    for (const PassDesc &pd : passes) {
-#if defined(NTT_EXPERIMENT)
-        if (pl->only_pass >= 0 && (int) (&pd - &passes.front()) != pl->only_pass) continue;  // timing experiment: outputs meaningless
-#endif
-        RoctxRange pass("lde pass", pd.contig, pd.s0, pd.log_m);
-        ntt::ErasedArgs a = base_args(pl, pd, d_out, d_out, batch);
-        if (&pd == &passes.front()) {  // expands while it loads: reads d_in (compact) only, writes d_out
+    return run_passes(pl, passes, 0, passes.size(), false, "lde pass", d_out, d_out, batch, out_layout, s, [&](ntt::ErasedArgs &a, size_t i) {
+        if (i == 0) {  // expands while it loads: reads d_in (compact) only, writes d_out
             a.lde_in = d_in;
             a.lde_s = pl->d_lde_s;
             a.lde_beta = beta;
         }
-        a.tw = pl->d_tw_fwd;
-        a.layout = out_layout;
-        hipError_t e = launch_fwd(pl, pd, a, s);
-        if (e != hipSuccess) return (int) e;
-    }
-    return NTT_OK;
+    });
 } NTT_GUARD_END
 
 int ntt_forward_profile(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int out_layout,
@@ -776,11 +717,7 @@ int ntt_forward_profile(ntt_plan_t pl, const void *d_in, void *d_out, size_t bat
     const void *src = d_in;
     hipError_t e = hipEventRecord(ev[0], s);
     for (size_t i = 0; i < np && e == hipSuccess; i++) {
-        const PassDesc &pd = passes[i];
-        ntt::ErasedArgs a = base_args(pl, pd, src, d_out, batch);
-        a.tw = pl->d_tw_fwd;
-        a.layout = out_layout;
-        e = launch_fwd(pl, pd, a, s);
+        e = launch_one(pl, passes[i], false, "fwd pass", src, d_out, batch, out_layout, s, [](ntt::ErasedArgs &) {});
         if (e == hipSuccess) e = hipEventRecord(ev[i + 1], s);
         src = d_out;
     }
@@ -796,8 +733,7 @@ int ntt_inverse(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int 
     if (rc) return rc;
     if (!pl->has_table) return NTT_E_NOTABLE;
     if (!pl->has_inv) return NTT_E_NOTINVERTIBLE;
-    if (in_layout != NTT_LAYOUT_NATURAL && in_layout != NTT_LAYOUT_AIE_BLOCK16) return NTT_E_ARG;
-    if (in_layout == NTT_LAYOUT_AIE_BLOCK16 && pl->logn < 4) return NTT_E_LAYOUT;
+    if ((rc = check_layout(pl, in_layout)) != NTT_OK) return rc;
     if (batch == 0) return NTT_OK;
     DeviceGuard g(pl->device);
     if (g.err != hipSuccess) return (int) g.err;
@@ -814,11 +750,7 @@ int ntt_pointwise_mul(ntt_plan_t pl, const void *d_a, const void *d_b, void *d_o
     DeviceGuard g(pl->device);
     if (g.err != hipSuccess) return (int) g.err;
     const size_t count = batch << pl->logn;
-    hipError_t e = pl->fk == FK_GL    ? ntt::launch_pointwise_gl(d_a, d_b, d_out, count, scale, (hipStream_t) stream)
-                   : pl->fk == FK_M64 ? ntt::launch_pointwise_m64(d_a, d_b, d_out, count, pl->p, pl->pinv64, pl->r2_64, scale,
-                                                                  (hipStream_t) stream)
-                                      : ntt::launch_pointwise_m32(d_a, d_b, d_out, count, (uint32_t) pl->p, pl->pinv,
-                                                                  pl->r2, (uint32_t) scale, (hipStream_t) stream);
+    const hipError_t e = ntt::launch_pointwise(pl->field, d_a, d_b, d_out, count, scale, (hipStream_t) stream);
     return (int) e;
 } NTT_GUARD_END
 
@@ -842,33 +774,21 @@ int ntt_polymul_negacyclic(ntt_plan_t pl, void *d_a, void *d_b, void *d_out, siz
     // Goldilocks, first (or only) pass of 7..12 stages: the radix-8 product kernel exists for that unit size.  A single-pass
     // size (2^7 <= N <= 2^12) is then ONE launch for the whole product: read a, read b, write c.
     // ... 4-byte words: radix-16 product kernel, unit sizes 2^6 .. 2^13 (any odd p: all three butterfly streams).
-    bool fused_mid = first.contig && (pl->fk == FK_GL    ? ntt::have_gl_product_mid(first.log_m)
-                                      : pl->fk == FK_M64 ? ntt::have_m64_product_mid(first.log_m)
-                                                         : ntt::have_m32_product_mid(first.log_m));
-    if (fused_mid) {
-        // the product launch is not sliced: beyond blockIdx.y's range (tens of millions of tiny polynomials) take the
-        // separate passes, whose launcher slices the batch.  The check IS the launcher's geometry call (product_fits).
-        fused_mid = pl->fk == FK_GL    ? ntt::gl_product_mid_fits(first.log_m, pl->logn, (uint32_t) batch, pl->target_wgs)
-                    : pl->fk == FK_M64 ? ntt::m64_product_mid_fits(first.log_m, pl->logn, (uint32_t) batch, pl->target_wgs)
-                                       : ntt::m32_product_mid_fits(first.log_m, pl->logn, (uint32_t) batch, pl->target_wgs);
-    }
-    if (fused_mid) {
+    // The product launch is not sliced: beyond blockIdx.y's range (tens of millions of tiny polynomials) take the separate
+    // passes, whose launcher slices the batch.  The check IS the launcher's geometry call (launch.h: product_mid_fits).
+    if (first.contig && ntt::product_mid_used(pl->field, first.log_m) &&
+        ntt::product_mid_fits(pl->field, first.log_m, pl->logn, (uint32_t) batch, pl->target_wgs)) {
         // The column passes (if any) of both unscaled inverse transforms, then ONE launch that runs
         // the last inverse pass of a and of b, the pointwise product * N^-1 and the first forward pass on each
         // 2^log_m-word unit while it is workgroup-resident (3 N words of HBM traffic instead of 7 N), then the
         // forward column passes.
-        for (size_t i = passes.size(); i-- > 1;) {
-            const PassDesc &pd = passes[i];
-            RoctxRange pass("product: inv pass", pd.contig, pd.s0, pd.log_m);
+        for (size_t i = passes.size(); i-- > 1;)
             for (int op = 0; op < (contiguous ? 1 : 2); op++) {
                 void *buf = op == 0 ? d_a : d_b;
-                ntt::ErasedArgs a = base_args(pl, pd, buf, buf, contiguous ? 2 * batch : batch);
-                a.tw = pl->d_tw_inv;
-                a.layout = NTT_LAYOUT_NATURAL;
-                hipError_t e = launch_inv(pl, pd, a, s);
+                hipError_t e = launch_one(pl, passes[i], true, "product: inv pass", buf, buf, contiguous ? 2 * batch : batch, NTT_LAYOUT_NATURAL, s,
+                                          [](ntt::ErasedArgs &) {});
                 if (e != hipSuccess) return (int) e;
             }
-        }
         {
             RoctxRange pass("product: fused middle", 1, 0, first.log_m);
             ntt::ErasedArgs a = base_args(pl, first, d_a, d_out, batch);
@@ -876,22 +796,12 @@ int ntt_polymul_negacyclic(ntt_plan_t pl, void *d_a, void *d_b, void *d_out, siz
             a.tw = pl->d_tw_inv;
             a.tw2 = pl->d_tw_fwd;
             a.layout = NTT_LAYOUT_NATURAL;
-            a.pw_scale = to_table_form(to_table_form(pl->ninv_plain % pl->p, pl->p, pl->word_bytes), pl->p, pl->word_bytes);
-            hipError_t e = pl->fk == FK_GL    ? ntt::launch_gl_product_mid(first.log_m, a, s)
-                           : pl->fk == FK_M64 ? ntt::launch_m64_product_mid(first.log_m, a, s)
-                                              : ntt::launch_m32_product_mid(first.log_m, a, s);
+            a.pw_scale = pw_scale_form(pl, pl->ninv_plain);
+            hipError_t e = ntt::launch_product_mid(first.log_m, a, s);
             if (e != hipSuccess) return (int) e;
         }
-        for (size_t i = 1; i < passes.size(); i++) {
-            const PassDesc &pd = passes[i];
-            RoctxRange pass("product: fwd pass", pd.contig, pd.s0, pd.log_m);
-            ntt::ErasedArgs a = base_args(pl, pd, d_out, d_out, batch);
-            a.tw = pl->d_tw_fwd;
-            a.layout = NTT_LAYOUT_NATURAL;
-            hipError_t e = launch_fwd(pl, pd, a, s);
-            if (e != hipSuccess) return (int) e;
-        }
-        return NTT_OK;
+        return run_passes(pl, passes, 1, passes.size(), false, "product: fwd pass", d_out, d_out, batch, NTT_LAYOUT_NATURAL, s,
+                          [](ntt::ErasedArgs &, size_t) {});
     }
     if (contiguous) {
         // the operands are one [2*batch][N] buffer: both unscaled inverse transforms as ONE launch per pass
@@ -940,10 +850,7 @@ int ntt_forward_stages(ntt_plan_t pl, const void *d_in, void *d_out, size_t batc
         if (e != hipSuccess) return (int) e;
     }
     for (int st = 0; st <= stage; st++) {
-        hipError_t e = pl->fk == FK_GL    ? ntt::launch_stage_gl(d_out, pl->d_tw_fwd, pl->logn, st, batch, s)
-                       : pl->fk == FK_M64 ? ntt::launch_stage_m64(d_out, pl->d_tw_fwd, pl->logn, st, batch, pl->p, pl->pinv64, pl->r2_64, s)
-                                          : ntt::launch_stage_m32(d_out, pl->d_tw_fwd, pl->logn, st, batch,
-                                                                  (uint32_t) pl->p, pl->pinv, pl->r2, s);
+        hipError_t e = ntt::launch_stage(pl->field, d_out, pl->d_tw_fwd, pl->logn, st, batch, s);
         if (e != hipSuccess) return (int) e;
     }
     return NTT_OK;

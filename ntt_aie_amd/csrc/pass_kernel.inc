@@ -1,13 +1,12 @@
-// pass_kernel.inc -- the __global__ wrapper around run_pass() and the switch that
-// instantiates it for one (field, direction).  Included by the four
-// kernels_<field>_<dir>.hip translation units, which define
-//   NTT_FIELD      ntt::FieldGL | ntt::FieldM32
+// pass_kernel.inc -- the __global__ wrapper around run_pass() and the launcher that instantiates it for every
+// configuration launch.h selects for one (field, direction).  Included by the six kernels_<field>_<dir>.hip
+// translation units, which define
+//   NTT_FIELD      ntt::FieldGL | ntt::FieldM32 | ntt::FieldM64
 //   NTT_INV        true | false
-//   NTT_LAUNCH_FN  launch_gl_fwd | ...
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
-#include "pass.h"
+#include "launch.h"
 
 namespace ntt {
 namespace {
@@ -123,55 +122,13 @@ void pass_kernel(PassArgs<Cfg> a) {
     }
 }
 
-template <class F>
-F make_field(const ErasedArgs &e);
-template <>
-FieldGL make_field<FieldGL>(const ErasedArgs &) {
-    return FieldGL{};
-}
-template <>
-FieldM32 make_field<FieldM32>(const ErasedArgs &e) {
-    return FieldM32{e.p, e.pinv, e.r2};
-}
-template <>
-FieldM64 make_field<FieldM64>(const ErasedArgs &e) {
-    return FieldM64{e.p64, e.pinv64, e.r2_64};
-}
-
 template <class Cfg>
 hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
     using W = typename Cfg::W;
-    PassArgs<Cfg> a;
-    a.in = (const W *) e.in;
-    a.out = (W *) e.out;
-    a.tw = (const W *) e.tw;
-    a.tw_sc = nullptr;
-    a.field = make_field<typename Cfg::F>(e);
-    a.n = e.n;
-    a.s0 = e.s0;
-    a.batch = e.batch;
-    a.layout = e.layout;
-    a.do_scale = e.do_scale;
-    a.scale = (W) e.scale;
-    a.dbg = e.dbg;
-    a.pg_stride = 1;
-    a.in2 = (const W *) e.in2;
-    a.pw_scale = (W) e.pw_scale;
-    a.skip_if = (const uint32_t *) e.skip_if;
-    // the fused expansion runs in its own kernels and nowhere else (never beside LDS-DMA or the register prefetch: PassCfg::LDE)
+    // the fused expansion runs in its own kernels and nowhere else (never beside LDS-DMA or the register prefetch: PassCfg::LDE);
+    // refused here before anything else, and again by the fill below, which the host index model shares
     if ((e.lde_beta != 0) != Cfg::LDE) return hipErrorInvalidValue;
-    if constexpr (Cfg::LDE) {
-        if (e.lde_beta < 1 || e.lde_beta > 4 || e.lde_beta >= e.n || e.s0 != 0 || !e.lde_in || !e.lde_s || e.in2) return hipErrorInvalidValue;
-        a.lde_in = (const W *) e.lde_in;
-        a.lde_s = (const W *) e.lde_s;
-        a.lde_beta = e.lde_beta;
-    }
-#if defined(NTT_PHASE_STAMPS)
-    a.stamps = (unsigned long long *) e.stamps;
-    a.stamp_records = e.stamp_records;
-#endif
-    PassGeom g = pass_geometry(e.n, e.s0, Cfg::LOG_M, Cfg::LOG_C, Cfg::LOG_U, Cfg::CONTIG, e.batch,
-                               e.target_wgs, Cfg::PPW_CAP);
+    PassGeom g = pass_geometry_of<Cfg>(e);
 #if defined(NTT_EXPERIMENT)
     if ((e.dbg & 0x1000) && g.grid_x == 1 && g.ppw == 1) {
         // EXPERIMENT (round 6, config 2): ONE generation of `cap` = dbg >> 16 workgroups for cap < groups <= 2 cap: the first
@@ -184,6 +141,8 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
         }
     }
 #endif
+    PassArgs<Cfg> a;
+    if (!fill_pass_args<Cfg>(e, g, a)) return hipErrorInvalidValue;  // launch.h: LDE argument ranges, do_scale without tw_sc, ...
     if (g.grid_y == 0) return hipSuccess;
     if (g.grid_y > 65535u) {
         // more polynomial groups than blockIdx.y can number (tiny N, batch beyond ~10^9): polynomials are
@@ -202,15 +161,8 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
         }
         return hipSuccess;
     }
-    a.ppw = g.ppw;
-    a.tp = g.tp;
-    a.log_ul = g.log_ul;
-    a.log_uh = g.log_uh;
-    a.log_up = g.log_up;
     if constexpr (fold_scale<Cfg>()) {
-        if (e.do_scale && e.tw_sc == nullptr) return hipErrorInvalidValue;  // these kernels have no scaling sweep
-        if (e.do_scale) {  // scaled inverse: N^-1 rides on stage 0 (no scaling sweep)
-            a.tw_sc = (const W *) e.tw_sc;
+        if (a.tw_sc != nullptr) {  // scaled inverse: N^-1 rides on stage 0 (no scaling sweep)
             hipLaunchKernelGGL((pass_kernel<Cfg, true>), dim3(g.grid_x, g.grid_y, 1), dim3(Cfg::NT, 1, 1), 0, s, a);
             return hipGetLastError();
         }
@@ -219,102 +171,16 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int LOG_M>
-using ContigCfg = PassCfg<NTT_FIELD, LOG_M, 0, true, NTT_INV, contig_preload_mask(LOG_M, sizeof(typename NTT_FIELD::W))>;
-// 13 stages on an 8192-word tile: 512 threads x 16 words, rounds of 4 + 4 + 4 + 1 stages.  4-byte words keep every round's
-// twiddles in registers (99 VGPRs); 8-byte words only the last round's single, wave-uniform one (the others are re-read
-// from L2 at the start of their round, as in the 12-stage radix-16 pass: 128 VGPRs, two workgroups per CU)
-using ContigCfg13 = PassCfg<NTT_FIELD, 13, 0, true, NTT_INV, sizeof(typename NTT_FIELD::W) == 4 ? 0xF : 0x8, 4, 9>;
-// 14 stages on a 16384-word tile of 4-byte words (64 KiB): ONE 1024-thread workgroup per CU, rounds of 4 + 4 + 4 + 2 stages, every
-// round's twiddles resident.  Pays only for the lazy butterflies (p < 2^30: N = 2^14 in one pass -21 % forward, -5 % inverse at
-// saturating batches; +3 % for a 32-bit prime, +20 % for one polynomial: profiles/r02_ab_13_stage_pass.txt), so the planner offers it
-// as a launch-time alternative for that modulus class above a batch threshold (plan.h: plan_alternatives)
-using ContigCfg14 = PassCfg<NTT_FIELD, 14, 0, true, NTT_INV, 0xF, 4, 10>;
-template <int LOG_M>
-using ContigCfgE8 = PassCfg<NTT_FIELD, LOG_M, 0, true, NTT_INV, 0xF, 3>;
-template <int LOG_M>
-using ContigCfgE8W = PassCfg<NTT_FIELD, LOG_M, 0, true, NTT_INV, 0xF, 3, 9>;  // 512 threads
-// forward pass with a fused pointwise product (a.in2): same kernels, tile staged by ordinary loads
-template <int LOG_M>
-using ContigCfgE8P = PassCfg<NTT_FIELD, LOG_M, 0, true, NTT_INV, 0xF, 3, 8, false>;
-template <int LOG_M>
-using ContigCfgE8WP = PassCfg<NTT_FIELD, LOG_M, 0, true, NTT_INV, 0xF, 3, 9, false>;
-template <int LOG_M>
-using ColCfg = ColPassCfg<NTT_FIELD, LOG_M, NTT_INV>;
-
 }  // namespace
 
-hipError_t NTT_LAUNCH_FN(bool contig, int log_m, const ErasedArgs &a, hipStream_t s) {
-    if (a.lde_beta != 0) {  // first pass of ntt_lde: the fused-expansion twin of this shape (pass.h: lde_dispatch)
-        if constexpr (NTT_INV) {
-            return hipErrorInvalidValue;
-        } else {
-            hipError_t err = hipErrorInvalidValue;
-            if (!contig || !lde_dispatch<NTT_FIELD>(log_m, a.s0 + log_m == a.n, [&](auto tag) { err = launch_cfg<typename decltype(tag)::Cfg>(a, s); }))
-                return hipErrorInvalidValue;
-            return err;
-        }
-    }
-    if (contig) {
-        if (log_m == 13) return launch_cfg<ContigCfg13>(a, s);
-        if (log_m == 14) {
-            if constexpr (sizeof(typename NTT_FIELD::W) == 4) return launch_cfg<ContigCfg14>(a, s);
-            else return hipErrorInvalidValue;
-        }
-        // PassDesc::variant 1: a single-pass unit of 2^10 .. 2^12 words on 512 threads x 8 words (radix-8 rounds; 8-byte forward: the
-        // LDS-DMA kernel that otherwise runs as the first pass of a two-pass plan) instead of 256 x 16 -- twice the waves for the same
-        // work, for launches too small to fill the SIMDs (plan.h: plan_alternatives).  Both layouts (pass.h: elem_off / lane_eff);
-        // a fused pointwise operand keeps the default kernel.
-        if (a.variant == 1 && a.in2 == nullptr) {
-            if (log_m == 10) return launch_cfg<ContigCfgE8W<10>>(a, s);
-            if (log_m == 11) return launch_cfg<ContigCfgE8W<11>>(a, s);
-            if (log_m == 12) return launch_cfg<ContigCfgE8W<12>>(a, s);
-        }
-        if (contig_log_e(log_m, sizeof(typename NTT_FIELD::W), a.s0 + log_m == a.n) == 3) {
-            if constexpr (sizeof(typename NTT_FIELD::W) == 8 && !NTT_INV) {
-                if (a.in2 != nullptr) {
-                    if (log_m == 7) return launch_cfg<ContigCfgE8P<7>>(a, s);
-                    if (log_m == 8) return launch_cfg<ContigCfgE8P<8>>(a, s);
-                    if (log_m == 9) return launch_cfg<ContigCfgE8P<9>>(a, s);
-                    if (log_m == 10) return launch_cfg<ContigCfgE8WP<10>>(a, s);
-                    if (log_m == 11) return launch_cfg<ContigCfgE8WP<11>>(a, s);
-                    return launch_cfg<ContigCfgE8WP<12>>(a, s);
-                }
-            }
-            if constexpr (sizeof(typename NTT_FIELD::W) == 8) {
-                if (log_m == 7) return launch_cfg<ContigCfgE8<7>>(a, s);
-                if (log_m == 8) return launch_cfg<ContigCfgE8<8>>(a, s);
-                if (log_m == 9) return launch_cfg<ContigCfgE8<9>>(a, s);
-                if (log_m == 10) return launch_cfg<ContigCfgE8W<10>>(a, s);
-                if (log_m == 11) return launch_cfg<ContigCfgE8W<11>>(a, s);
-                return launch_cfg<ContigCfgE8W<12>>(a, s);
-            }
-        }
-        switch (log_m) {
-            case 1: return launch_cfg<ContigCfg<1>>(a, s);
-            case 2: return launch_cfg<ContigCfg<2>>(a, s);
-            case 3: return launch_cfg<ContigCfg<3>>(a, s);
-            case 4: return launch_cfg<ContigCfg<4>>(a, s);
-            case 5: return launch_cfg<ContigCfg<5>>(a, s);
-            case 6: return launch_cfg<ContigCfg<6>>(a, s);
-            case 7: return launch_cfg<ContigCfg<7>>(a, s);
-            case 8: return launch_cfg<ContigCfg<8>>(a, s);
-            case 9: return launch_cfg<ContigCfg<9>>(a, s);
-            case 10: return launch_cfg<ContigCfg<10>>(a, s);
-            case 11: return launch_cfg<ContigCfg<11>>(a, s);
-            case 12: return launch_cfg<ContigCfg<12>>(a, s);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (log_m) {
-        case 4: return launch_cfg<ColCfg<4>>(a, s);
-        case 5: return launch_cfg<ColCfg<5>>(a, s);
-        case 6: return launch_cfg<ColCfg<6>>(a, s);
-        case 7: return launch_cfg<ColCfg<7>>(a, s);
-        case 8: return launch_cfg<ColCfg<8>>(a, s);
-        case 9: return launch_cfg<ColCfg<9>>(a, s);  // 512 rows x one 128-byte segment: N = 2^22 = 13 + 9 in two passes
-        default: return hipErrorInvalidValue;
-    }
+// the kernel launch.h's pass_dispatch selects for this pass.  (This definition names launch_cfg of THIS unit's anonymous namespace:
+// it is explicitly instantiated below for the unit's one (field, direction) and for nothing else -- see kernels.h)
+template <class F, bool INV>
+hipError_t launch_pass_of(bool contig, int log_m, const ErasedArgs &a, hipStream_t s) {
+    hipError_t err = hipErrorInvalidValue;
+    if (!pass_dispatch<F, INV>(contig, log_m, a, [&](auto tag) { err = launch_cfg<typename decltype(tag)::Cfg>(a, s); })) return hipErrorInvalidValue;
+    return err;
 }
+template hipError_t launch_pass_of<NTT_FIELD, NTT_INV>(bool, int, const ErasedArgs &, hipStream_t);
 
 }  // namespace ntt

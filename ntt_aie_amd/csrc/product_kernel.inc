@@ -1,10 +1,9 @@
 // product_kernel.inc -- executor, __global__ wrapper and launcher of the product's fused middle pass (pass.h:
-// run_product_pass), shared by kernels_gl_product.hip and kernels_m32_product.hip.
+// run_product_pass).  Included by the three kernels_<field>_product.hip translation units, which define NTT_FIELD.
 #include <hip/hip_runtime.h>
-#include <string.h>
 
 #include "kernels.h"
-#include "pass.h"
+#include "launch.h"
 
 namespace ntt {
 namespace {
@@ -65,74 +64,29 @@ void product_kernel(PassArgs<CI> aa, const typename CI::W *in_b, PassArgs<CF> af
     }
 }
 
-template <class F>
-F product_field(const ErasedArgs &e);
-template <>
-FieldGL product_field<FieldGL>(const ErasedArgs &) {
-    return FieldGL{};
-}
-template <>
-FieldM32 product_field<FieldM32>(const ErasedArgs &e) {
-    return FieldM32{e.p, e.pinv, e.r2};
-}
-template <>
-FieldM64 product_field<FieldM64>(const ErasedArgs &e) {
-    return FieldM64{e.p64, e.pinv64, e.r2_64};
-}
-
-// does the product launch of this unit size cover `batch` polynomials in one grid (blockIdx.y <= 65535)?  The SAME geometry call
-// launch_product makes -- the pre-check of ntt_polymul_negacyclic goes through here, so the two cannot disagree
-template <class PC>
-bool product_fits(int n, uint32_t batch, uint32_t target_wgs) {
-    const PassGeom g = pass_geometry(n, 0, PC::CI::LOG_M, 0, PC::CI::LOG_U, true, batch, target_wgs);
-    return g.grid_y <= 65535u;
-}
-
 template <class PC>
 hipError_t launch_product(const ErasedArgs &e, hipStream_t s) {
     using CI = typename PC::CI;
     using CF = typename PC::CF;
-    using W = typename CI::W;
-    constexpr int LOG_M = CI::LOG_M;
-    PassGeom g = pass_geometry(e.n, 0, LOG_M, 0, CI::LOG_U, true, e.batch, e.target_wgs);
+    const PassGeom g = product_geometry<PC>(e.n, e.batch, e.target_wgs);
     if (g.grid_y == 0) return hipSuccess;
-    if (g.grid_y > 65535u) return hipErrorInvalidValue;  // callers fall back to the separate passes
+    if (g.grid_y > 65535u) return hipErrorInvalidValue;  // callers fall back to the separate passes (launch.h: product_mid_fits)
     PassArgs<CI> aa;
-    ::memset((void *) &aa, 0, sizeof(aa));
-    aa.in = (const W *) e.in;
-    aa.out = nullptr;
-    aa.tw = (const W *) e.tw;
-    aa.field = product_field<typename CI::F>(e);
-    aa.n = e.n;
-    aa.s0 = 0;
-    aa.batch = e.batch;
-    aa.ppw = g.ppw;
-    aa.tp = g.tp;
-    aa.log_ul = g.log_ul;
-    aa.log_uh = g.log_uh;
-    aa.log_up = g.log_up;
-    aa.layout = LAYOUT_NATURAL;
-    aa.pg_stride = 1;
     PassArgs<CF> af;
-    ::memset((void *) &af, 0, sizeof(af));
-    af.in = nullptr;
-    af.out = (W *) e.out;
-    af.tw = (const W *) e.tw2;
-    af.field = product_field<typename CF::F>(e);
-    af.n = e.n;
-    af.s0 = 0;
-    af.batch = e.batch;
-    af.ppw = g.ppw;
-    af.tp = g.tp;
-    af.log_ul = g.log_ul;
-    af.log_uh = g.log_uh;
-    af.log_up = g.log_up;
-    af.layout = e.layout;
-    af.pg_stride = 1;
-    af.pw_scale = (W) e.pw_scale;
-    hipLaunchKernelGGL((product_kernel<CI, CF>), dim3(g.grid_x, g.grid_y, 1), dim3(CI::NT, 1, 1), 0, s, aa, (const W *) e.in2, af);
+    fill_product_args<PC>(e, g, aa, af);
+    hipLaunchKernelGGL((product_kernel<CI, CF>), dim3(g.grid_x, g.grid_y, 1), dim3(CI::NT, 1, 1), 0, s, aa, (const typename CI::W *) e.in2, af);
     return hipGetLastError();
 }
 
 }  // namespace
+
+// every unit size with a kernel (launch.h: product_dispatch); instantiated for this unit's field only, as launch_pass_of is (kernels.h)
+template <class F>
+hipError_t launch_product_mid_of(int log_m, const ErasedArgs &a, hipStream_t s) {
+    hipError_t err = hipErrorInvalidValue;
+    product_dispatch<F>(log_m, [&](auto tag) { err = launch_product<typename decltype(tag)::Cfg>(a, s); });
+    return err;
+}
+template hipError_t launch_product_mid_of<NTT_FIELD>(int, const ErasedArgs &, hipStream_t);
+
 }  // namespace ntt

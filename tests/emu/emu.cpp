@@ -6,17 +6,7 @@
 // index rules, the LDS exchange pattern, the pass planner and the modular
 // arithmetic can be checked against the oracle on a machine without a GPU.
 // It is not a CPU fallback: nothing in the product loads this library.
-#include <stdint.h>
-#include <string.h>
-
-#include <vector>
-
-#define NTT_EMU_TRACK 1
-#include <stdio.h>
-#include <stdlib.h>
-
-#include "../../ntt_aie_amd/csrc/pass.h"
-#include "../../ntt_aie_amd/csrc/plan.h"
+#include "emu_exec.h"
 
 using namespace ntt;
 using namespace ntt::host;
@@ -36,328 +26,31 @@ static int g_no_track = 0;
 
 namespace {
 
-// LDS hazard tracker (pass.h: NTT_LDS_ACCESS).  epoch = number of WORKGROUP barriers so far.  A word may be read by a wave
-// only if its last write is this wave's own or older than the last barrier; it may be written only if, in addition, every
-// read of it since the last barrier was this wave's own.  Wave-local syncs do not advance the epoch: LDS operations of one
-// wave execute in order, so same-wave accesses are always fine.  A violation aborts the process (the test then fails).
-struct EmuLdsTrack : ntt::LdsTrack {
-    struct St {
-        int w_wave = -1, w_epoch = -1, r_wave = -1, r_epoch = -1;  // r_wave -2: several waves read it in r_epoch
-    };
-    std::vector<St> st;
-    const char *base = nullptr;
-    size_t word_bytes = 1;
-    int epoch = 0;
-    const char *what = "";
-    void reset(const void *tile, size_t words, size_t wb) {  // a new workgroup
-        base = (const char *) tile;
-        word_bytes = wb;
-        st.assign(words, St());
-        epoch = 0;
-    }
-    void barrier() { ++epoch; }
-    void access(const void *word, uint32_t tid, bool write) override {
-        const int wave = (int) (tid >> 6);
-        const size_t idx = (size_t) ((const char *) word - base) / word_bytes;
-        if ((const char *) word < base || idx >= st.size()) return;  // not the tile (the product pass's twiddle tables)
-        St &s = st[idx];
-        const bool raw = s.w_epoch == epoch && s.w_wave != wave && s.w_wave != -1;
-        const bool war = write && s.r_epoch == epoch && s.r_wave != wave && s.r_wave != -1;
-        if (raw || war) {
-            fprintf(stderr, "LDS hazard in %s: wave %d %s a word that wave %d %s since the last workgroup barrier (epoch %d)\n", what, wave,
-                    write ? "writes" : "reads", raw ? s.w_wave : s.r_wave, raw ? "wrote" : "read", epoch);
-            abort();
-        }
-        if (write) {
-            s.w_wave = wave;
-            s.w_epoch = epoch;
-        } else if (s.r_epoch == epoch && s.r_wave != wave) {
-            s.r_wave = -2;
-        } else {
-            s.r_wave = wave;
-            s.r_epoch = epoch;
-        }
-    }
-};
-
-template <class Cfg>
-struct EmuExec {
-    static constexpr bool early_ok = true;
-    std::vector<Ctx<Cfg>> ctx;
-    std::vector<typename Cfg::W> tile;
-    uint32_t bx, by;
-    EmuExec() : ctx(Cfg::NT), tile(Cfg::DMA ? 2 * Cfg::TILE_WORDS : Cfg::LDS_WORDS) {}
-    void init(const PassArgs<Cfg> &a) {
-        for (int t = 0; t < Cfg::NT; t++) phase_init<Cfg>(ctx[t], a, (uint32_t) t, bx, by);
-    }
-    void init_indices(const PassArgs<Cfg> &a) {
-        for (int t = 0; t < Cfg::NT; t++) phase_init<Cfg, false>(ctx[t], a, (uint32_t) t, bx, by);
-    }
-    // only_wave >= 0: step just that wave's 64 lanes (used to prove WAVE_LOCAL passes never read
-    // another wave's LDS words: the four waves are then run one after the other, start to finish)
-    int only_wave = -1;
-    template <class Fn>
-    void each(Fn &&f) {
-        const int lo = only_wave < 0 ? 0 : 64 * only_wave, hi = only_wave < 0 ? Cfg::NT : lo + 64;
-        for (int t = lo; t < hi; t++) f(ctx[t]);
-    }
-    EmuLdsTrack tr;
-    void sync(std::false_type) { tr.barrier(); }
-    void sync(std::true_type) {}
-    uint32_t pg_base() const { return ctx[0].pg_base; }
-    int ppw() const { return ctx[0].ppw; }
-    bool iter_begin(int) { return true; }
-    void iter_done(int) {}
-    void pass_done(int) {}
-    typename Cfg::W *lds() { return tile.data(); }
-};
-
-// host twin of GpuProductExec (kernels_gl_product.hip): all contexts of the workgroup stepped phase by phase
-template <class CI, class CF>
-struct EmuProductExec {
-    using W = typename CI::W;
-    std::vector<Ctx<CI>> ci;
-    std::vector<Ctx<CF>> cf;
-    std::vector<W> keep, pre, tile, tab_i, tab_f;
-    uint32_t bx, by;
-    int only_wave = -1;
-    EmuProductExec()
-        : ci(CI::NT), cf(CI::NT), keep((size_t) CI::NT * CI::E), pre((size_t) CI::NT * CI::E), tile(CI::LDS_WORDS),
-          tab_i(tw_table_words<CI>()), tab_f(tw_table_words<CF>()) {}
-    void init(const PassArgs<CI> &aa, const PassArgs<CF> &af) {
-        for (int t = 0; t < CI::NT; t++) {
-            phase_init<CI>(ci[t], aa, (uint32_t) t, bx, by);
-            phase_init<CF>(cf[t], af, (uint32_t) t, bx, by);
-        }
-    }
-    int lo() const { return only_wave < 0 ? 0 : 64 * only_wave; }
-    int hi() const { return only_wave < 0 ? CI::NT : 64 * only_wave + 64; }
-    template <class Fn>
-    void eachI(Fn &&f) { for (int t = lo(); t < hi(); t++) f(ci[t]); }
-    template <class Fn>
-    void eachF(Fn &&f) { for (int t = lo(); t < hi(); t++) f(cf[t]); }
-    template <class Fn>
-    void eachIF(Fn &&f) { for (int t = lo(); t < hi(); t++) f(ci[t], cf[t], &keep[(size_t) t * CI::E], &pre[(size_t) t * CI::E]); }
-    EmuLdsTrack tr;
-    void sync(std::false_type) { tr.barrier(); }
-    void sync(std::true_type) {}
-    uint32_t pg_base() const { return ci[0].pg_base; }
-    int ppw() const { return ci[0].ppw; }
-    W *lds() { return tile.data(); }
-    W *tabI() { return tab_i.data(); }
-    W *tabF() { return tab_f.data(); }
-};
-
-struct Erased {
-    const void *in;
-    void *out;
-    const void *tw;
-    const void *tw_sc;  // Goldilocks scaled inverse: stage-0 twiddles * N^-1 (N/2 words), as ntt_api.hip prepares them
-    uint32_t p, pinv, r2;
-    uint64_t p64, pinv64, r2_64;  // FieldM64
-    int n, s0;
-    uint32_t batch;
-    int layout, do_scale;
-    uint64_t scale;
-    uint32_t target_wgs;
-    const void *in2;
-    uint64_t pw_scale;
-    int variant;  // PassDesc::variant of the pass being run (pass_kernel.inc: 1 = 4-byte CONTIG 10..12 stages on 512 threads x 8 words)
-};
-
-template <class F>
-F make_field(const Erased &e);
-template <>
-FieldGL make_field<FieldGL>(const Erased &) {
-    return FieldGL{};
-}
-template <>
-FieldM32 make_field<FieldM32>(const Erased &e) {
-    return FieldM32{e.p, e.pinv, e.r2};
-}
-template <>
-FieldM64 make_field<FieldM64>(const Erased &e) {
-    return FieldM64{e.p64, e.pinv64, e.r2_64};
-}
-
-template <class PC>
-int run_product_mid(int n, uint32_t batch, uint32_t target_wgs, const void *a_in_, const void *b_in_, void *out_,
-                    const void *tw_inv_, const void *tw_fwd_, uint64_t pw_scale, const Erased &fe) {
-    using CI = typename PC::CI;
-    using CF = typename PC::CF;
-    using W = typename CI::W;
-    constexpr int LOG_M = CI::LOG_M;
-    const W *a_in = (const W *) a_in_, *b_in = (const W *) b_in_, *tw_inv = (const W *) tw_inv_, *tw_fwd = (const W *) tw_fwd_;
-    W *out = (W *) out_;
-    PassGeom g = pass_geometry(n, 0, LOG_M, 0, CI::LOG_U, true, batch, target_wgs);
-    PassArgs<CI> aa;
-    memset((void *) &aa, 0, sizeof(aa));
-    aa.in = a_in;
-    aa.tw = tw_inv;
-    aa.field = make_field<typename CI::F>(fe);
-    aa.n = n;
-    aa.batch = batch;
-    aa.ppw = g.ppw;
-    aa.tp = g.tp;
-    aa.log_ul = g.log_ul;
-    aa.log_uh = g.log_uh;
-    aa.log_up = g.log_up;
-    aa.pg_stride = 1;
-    PassArgs<CI> ab = aa;
-    ab.in = b_in;
-    PassArgs<CF> af;
-    memset((void *) &af, 0, sizeof(af));
-    af.out = out;
-    af.tw = tw_fwd;
-    af.field = make_field<typename CF::F>(fe);
-    af.n = n;
-    af.batch = batch;
-    af.ppw = g.ppw;
-    af.tp = g.tp;
-    af.log_ul = g.log_ul;
-    af.log_uh = g.log_uh;
-    af.log_up = g.log_up;
-    af.pg_stride = 1;
-    af.pw_scale = (W) pw_scale;
-    EmuProductExec<CI, CF> ex;
-    for (uint32_t by = 0; by < g.grid_y; by++)
-        for (uint32_t bx = 0; bx < g.grid_x; bx++) {
-            ex.bx = bx;
-            ex.by = by;
-            memset(ex.tile.data(), 0xA5, ex.tile.size() * sizeof(W));
-            ex.tr.reset(ex.tile.data(), ex.tile.size(), sizeof(W));
-            ex.tr.what = "product pass";
-            ntt::lds_track() = g_no_track ? nullptr : &ex.tr;
-            run_product_pass<CI, CF>(ex, aa, ab, af);
-            ntt::lds_track() = nullptr;
-        }
-    return 0;
-}
-
-
-template <class Cfg>
-int run_cfg(const Erased &e) {
-    using W = typename Cfg::W;
-    PassArgs<Cfg> a;
-    a.in = (const W *) e.in;
-    a.out = (W *) e.out;
-    a.tw = (const W *) e.tw;
-    a.tw_sc = nullptr;
-    constexpr bool CAN_FOLD = fold_scale<Cfg>();
-    const bool sc = CAN_FOLD && e.do_scale;  // the launcher's rule (pass_kernel.inc: launch_cfg)
-    if (sc) {
-        if (!e.tw_sc) return -2;
-        a.tw_sc = (const W *) e.tw_sc;
-    }
-    a.field = make_field<typename Cfg::F>(e);
-    a.n = e.n;
-    a.s0 = e.s0;
-    a.batch = e.batch;
-    a.layout = e.layout;
-    a.do_scale = e.do_scale;
-    a.scale = (W) e.scale;
-    a.dbg = 0;
-    a.pg_stride = 1;
-    a.in2 = (const W *) e.in2;
-    a.pw_scale = (W) e.pw_scale;
-    a.skip_if = nullptr;
-    PassGeom g = pass_geometry(e.n, e.s0, Cfg::LOG_M, Cfg::LOG_C, Cfg::LOG_U, Cfg::CONTIG, e.batch, e.target_wgs, Cfg::PPW_CAP);
-    a.ppw = g.ppw;
-    a.tp = g.tp;
-    a.log_ul = g.log_ul;
-    a.log_uh = g.log_uh;
-    a.log_up = g.log_up;
-    EmuExec<Cfg> ex;
-    for (uint32_t by = 0; by < g.grid_y; by++)
-        for (uint32_t bx = 0; bx < g.grid_x; bx++) {
-            ex.bx = bx;
-            ex.by = by;
-            // poison the tile: a read of a word nobody wrote this launch shows up as garbage
-            memset(ex.tile.data(), 0xA5, ex.tile.size() * sizeof(W));
-            ex.tr.reset(ex.tile.data(), ex.tile.size(), sizeof(W));
-            ex.tr.what = Cfg::CONTIG ? "CONTIG pass" : "column pass";
-            ntt::lds_track() = g_no_track ? nullptr : &ex.tr;
-            auto go = [&]() {
-                if constexpr (CAN_FOLD) {
-                    if (sc) return run_pass<Cfg, EmuExec<Cfg>, -1, true>(ex, a);
-                }
-                return run_pass<Cfg>(ex, a);
-            };
-            if constexpr (Cfg::WAVE_LOCAL) {
-                for (int w = 0; w < Cfg::NT / 64; w++) {
-                    ex.only_wave = w;
-                    go();
-                    memset(ex.tile.data(), 0x5A, ex.tile.size() * sizeof(W));  // nothing may survive
-                }
-            } else {
-                go();
-            }
-            ntt::lds_track() = nullptr;
-        }
-    return 0;
-}
-
+// the kernel the GPU launcher runs for this pass (csrc/launch.h: pass_dispatch), stepped on the host; -1 = no such kernel
 template <class F, bool INV>
-int dispatch(bool contig, int log_m, const Erased &e) {
-#define CASE_CONTIG(M)                                                                                \
-    case M:                                                                                           \
-        return run_cfg<PassCfg<F, M, 0, true, INV, contig_preload_mask(M, sizeof(typename F::W))>>(e);
-#define CASE_COL(M) \
-    case M:         \
-        return run_cfg<ColPassCfg<F, M, INV>>(e);
-    if (contig) {
-        if (log_m == 13) return run_cfg<PassCfg<F, 13, 0, true, INV, sizeof(typename F::W) == 4 ? 0xF : 0x8, 4, 9>>(e);  // pass_kernel.inc: ContigCfg13
-        if (log_m == 14) {  // pass_kernel.inc: ContigCfg14 (4-byte words only)
-            if constexpr (sizeof(typename F::W) == 4) return run_cfg<PassCfg<F, 14, 0, true, INV, 0xF, 4, 10>>(e);
-            else return -1;
-        }
-        // pass_kernel.inc: the wide radix-8 variant of the single-pass sizes 2^10 .. 2^12 (same conditions as there)
-        if (e.variant == 1 && e.in2 == nullptr) {
-            if (log_m == 10) return run_cfg<PassCfg<F, 10, 0, true, INV, 0xF, 3, 9>>(e);
-            if (log_m == 11) return run_cfg<PassCfg<F, 11, 0, true, INV, 0xF, 3, 9>>(e);
-            if (log_m == 12) return run_cfg<PassCfg<F, 12, 0, true, INV, 0xF, 3, 9>>(e);
-        }
-        if (contig_log_e(log_m, sizeof(typename F::W), e.s0 + log_m == e.n) == 3) {
-            if constexpr (!INV) {
-                if (e.in2 != nullptr) {  // fused product: the non-DMA twins (pass_kernel.inc)
-                    if (log_m == 7) return run_cfg<PassCfg<F, 7, 0, true, INV, 0xF, 3, 8, false>>(e);
-                    if (log_m == 8) return run_cfg<PassCfg<F, 8, 0, true, INV, 0xF, 3, 8, false>>(e);
-                    if (log_m == 9) return run_cfg<PassCfg<F, 9, 0, true, INV, 0xF, 3, 8, false>>(e);
-                    if (log_m == 10) return run_cfg<PassCfg<F, 10, 0, true, INV, 0xF, 3, 9, false>>(e);
-                    if (log_m == 11) return run_cfg<PassCfg<F, 11, 0, true, INV, 0xF, 3, 9, false>>(e);
-                    return run_cfg<PassCfg<F, 12, 0, true, INV, 0xF, 3, 9, false>>(e);
-                }
-            }
-            if (log_m == 7) return run_cfg<PassCfg<F, 7, 0, true, INV, 0xF, 3>>(e);
-            if (log_m == 8) return run_cfg<PassCfg<F, 8, 0, true, INV, 0xF, 3>>(e);
-            if (log_m == 9) return run_cfg<PassCfg<F, 9, 0, true, INV, 0xF, 3>>(e);
-            if (log_m == 10) return run_cfg<PassCfg<F, 10, 0, true, INV, 0xF, 3, 9>>(e);
-            if (log_m == 11) return run_cfg<PassCfg<F, 11, 0, true, INV, 0xF, 3, 9>>(e);
-            return run_cfg<PassCfg<F, 12, 0, true, INV, 0xF, 3, 9>>(e);
-        }
-        switch (log_m) {
-            CASE_CONTIG(1) CASE_CONTIG(2) CASE_CONTIG(3) CASE_CONTIG(4) CASE_CONTIG(5) CASE_CONTIG(6)
-            CASE_CONTIG(7) CASE_CONTIG(8) CASE_CONTIG(9) CASE_CONTIG(10) CASE_CONTIG(11) CASE_CONTIG(12)
-            default: return -1;
-        }
-    }
-    switch (log_m) {
-        CASE_COL(4) CASE_COL(5) CASE_COL(6) CASE_COL(7) CASE_COL(8) CASE_COL(9)
-        default: return -1;
-    }
+int dispatch(bool contig, int log_m, const ErasedArgs &e) {
+    int rc = -1;
+    pass_dispatch<F, INV>(contig, log_m, e, [&](auto tag) { rc = emu::run_pass_launch<typename decltype(tag)::Cfg>(e, !g_no_track); });
+    return rc;
+}
+template <class F>
+int dispatch_product(int log_m, const ErasedArgs &e) {
+    int rc = -1;
+    product_dispatch<F>(log_m, [&](auto tag) { rc = emu::run_product_launch<typename decltype(tag)::Cfg>(e, !g_no_track); });
+    return rc;
 }
 
 // the pass of one family (see EMU_PARTS)
-int dispatch_family(bool m64, int word_bytes, bool inverse, bool contig, int log_m, const Erased &e) {
-    (void) contig; (void) log_m; (void) e;
-    if (m64) {
+int dispatch_family(bool inverse, bool contig, int log_m, const ErasedArgs &e) {
+    (void) contig; (void) log_m;
+    if (e.field.kind == FK_M64) {
 #if EMU_HAS(2)
         if (!inverse) return dispatch<FieldM64, false>(contig, log_m, e);
 #endif
 #if EMU_HAS(3)
         if (inverse) return dispatch<FieldM64, true>(contig, log_m, e);
 #endif
-    } else if (word_bytes == 8) {
+    } else if (e.field.kind == FK_GL) {
 #if EMU_HAS(0)
         if (!inverse) return dispatch<FieldGL, false>(contig, log_m, e);
 #endif
@@ -372,6 +65,21 @@ int dispatch_family(bool m64, int word_bytes, bool inverse, bool contig, int log
         if (inverse) return dispatch<FieldM32, true>(contig, log_m, e);
 #endif
     }
+    return EMU_ABSENT;
+}
+
+// the fused product middle of one family
+int dispatch_product_family(int log_m, const ErasedArgs &e) {
+    (void) log_m;
+#if EMU_HAS(7)
+    if (e.field.kind == FK_M64) return dispatch_product<FieldM64>(log_m, e);
+#endif
+#if EMU_HAS(6)
+    if (e.field.kind == FK_GL) return dispatch_product<FieldGL>(log_m, e);
+#endif
+#if EMU_HAS(8)
+    if (e.field.kind == FK_M32) return dispatch_product<FieldM32>(log_m, e);
+#endif
     return EMU_ABSENT;
 }
 
@@ -428,19 +136,9 @@ int emu_transform(int word_bytes, int logn, uint64_t p, const void *T_plain, con
         }
         if (s0 != logn) return -1;
     }
-    Erased e;
+    ErasedArgs e;
     memset(&e, 0, sizeof(e));
-    e.p = (uint32_t) p;
-    if (word_bytes == 4) {
-        e.pinv = mont_pinv((uint32_t) p);
-        e.r2 = mont_r2((uint32_t) p);
-    }
-    const bool m64 = word_bytes == 8 && p != GOLDILOCKS;  // general odd 64-bit modulus (ntt_api.hip: FK_M64)
-    e.p64 = p;
-    if (m64) {
-        e.pinv64 = mont_pinv64(p);
-        e.r2_64 = mont_r2_64(p);
-    }
+    e.field = field_params(word_bytes, p);
     e.n = logn;
     e.batch = batch;
     e.layout = layout;
@@ -457,7 +155,7 @@ int emu_transform(int word_bytes, int logn, uint64_t p, const void *T_plain, con
         e.s0 = passes[i].s0;
         e.variant = passes[i].contig ? (contig_variant ? contig_variant : passes[i].variant) : 0;
         e.do_scale = (inverse && scale && i == 0) ? 1 : 0;
-        const int rc = dispatch_family(m64, word_bytes, inverse != 0, passes[i].contig, passes[i].log_m, e);
+        const int rc = dispatch_family(inverse != 0, passes[i].contig, passes[i].log_m, e);
         if (rc) return rc;
         cur = out;
     }
@@ -475,13 +173,10 @@ int emu_forward_product(int word_bytes, int logn, uint64_t p, const void *T_plai
         t32[i] = (uint32_t) to_table_form(t, p, 4 == word_bytes ? 4 : 8);
         t64[i] = to_table_form(t, p, 8);
     }
-    Erased e;
+    ErasedArgs e;
     memset(&e, 0, sizeof(e));
-    e.p = (uint32_t) p;
-    if (word_bytes == 4) {
-        e.pinv = mont_pinv((uint32_t) p);
-        e.r2 = mont_r2((uint32_t) p);
-    }
+    // 8-byte words: this entry point has always driven the Goldilocks family whatever p is (its callers pass that prime only)
+    e.field = word_bytes == 8 ? FieldParams{FK_GL, p, 0, 0} : field_params(word_bytes, p);
     e.n = logn;
     e.batch = batch;
     e.target_wgs = target_wgs;
@@ -494,7 +189,7 @@ int emu_forward_product(int word_bytes, int logn, uint64_t p, const void *T_plai
         e.s0 = passes[i].s0;
         e.in2 = i == 0 ? in2 : nullptr;
         e.pw_scale = to_table_form(to_table_form(scale % p, p, word_bytes), p, word_bytes);
-        const int rc = dispatch_family(false, word_bytes, false, passes[i].contig, passes[i].log_m, e);
+        const int rc = dispatch_family(false, passes[i].contig, passes[i].log_m, e);
         if (rc) return rc;
         cur = out;
     }
@@ -523,20 +218,11 @@ int emu_polymul_fused(int word_bytes, int logn, uint64_t p, const void *T_plain,
     const void *ti = word_bytes == 4 ? (const void *) ti32.data() : (const void *) ti64.data();
     const std::vector<PassDesc> passes = plan_passes(logn, word_bytes);
     const int m0 = passes[0].log_m;
-    if (word_bytes == 8 ? (m0 < 7 || m0 > 12) : (m0 < 5 || m0 > 13)) return -1;  // unit sizes the product kernels exist for
-    Erased e;
+    ErasedArgs e;
     memset(&e, 0, sizeof(e));
-    e.p = (uint32_t) p;
-    if (word_bytes == 4) {
-        e.pinv = mont_pinv((uint32_t) p);
-        e.r2 = mont_r2((uint32_t) p);
-    }
-    const bool m64 = word_bytes == 8 && p != GOLDILOCKS;
-    e.p64 = p;
-    if (m64) {
-        e.pinv64 = mont_pinv64(p);
-        e.r2_64 = mont_r2_64(p);
-    }
+    e.field = field_params(word_bytes, p);
+    // unit sizes the product kernels exist for (launch.h: product_dispatch), asked before a and b are touched
+    if (!with_field(e.field, [&](auto f) { return product_dispatch<decltype(f)>(m0, [](auto) {}); })) return -1;
     e.n = logn;
     e.batch = batch;
     e.target_wgs = target_wgs;
@@ -546,47 +232,27 @@ int emu_polymul_fused(int word_bytes, int logn, uint64_t p, const void *T_plain,
             e.out = buf;
             e.tw = ti;
             e.s0 = passes[i].s0;
-            const int rc = dispatch_family(m64, word_bytes, true, passes[i].contig, passes[i].log_m, e);
+            const int rc = dispatch_family(true, passes[i].contig, passes[i].log_m, e);
             if (rc) return rc;
         }
     const uint64_t ninv = powmod(p / 2 + 1, (uint64_t) logn, p);
-    const uint64_t pw = to_table_form(to_table_form(ninv, p, word_bytes), p, word_bytes);
-    int rc = EMU_ABSENT;
-    if (m64) {
-#if EMU_HAS(7)
-        switch (m0) {
-#define PM(M) case M: rc = run_product_mid<ProductCfg<M, FieldM64>>(logn, batch, target_wgs, a, b, out, ti, tf, pw, e); break;
-            PM(7) PM(8) PM(9) PM(10) PM(11) PM(12)
-#undef PM
-            default: return -1;
-        }
-#endif
-    } else if (word_bytes == 8) {
-#if EMU_HAS(6)
-        switch (m0) {
-#define PM(M) case M: rc = run_product_mid<ProductCfg<M>>(logn, batch, target_wgs, a, b, out, ti, tf, pw, e); break;
-            PM(7) PM(8) PM(9) PM(10) PM(11) PM(12)
-#undef PM
-            default: return -1;
-        }
-#endif
-    } else {
-#if EMU_HAS(8)
-        switch (m0) {
-#define PM(M) case M: rc = run_product_mid<ProductCfgM32<M>>(logn, batch, target_wgs, a, b, out, ti, tf, pw, e); break;
-            PM(5) PM(6) PM(7) PM(8) PM(9) PM(10) PM(11) PM(12) PM(13)
-#undef PM
-            default: return -1;
-        }
-#endif
-    }
+    e.in = a;
+    e.in2 = b;
+    e.out = out;
+    e.tw = ti;
+    e.tw2 = tf;
+    e.s0 = 0;
+    e.pw_scale = to_table_form(to_table_form(ninv, p, word_bytes), p, word_bytes);
+    int rc = dispatch_product_family(m0, e);
+    e.in2 = nullptr;
+    e.pw_scale = 0;
     if (rc) return rc;
     for (size_t i = 1; i < passes.size(); i++) {
         e.in = out;
         e.out = out;
         e.tw = tf;
         e.s0 = passes[i].s0;
-        rc = dispatch_family(m64, word_bytes, false, passes[i].contig, passes[i].log_m, e);
+        rc = dispatch_family(false, passes[i].contig, passes[i].log_m, e);
         if (rc) return rc;
     }
     return 0;
@@ -633,7 +299,7 @@ int emu_geometry(int n, int s0, int log_m, int log_c, int log_u, int contig, uin
     PassGeom g = pass_geometry(n, s0, log_m, log_c, log_u, contig != 0, batch, target_wgs, ppw_cap);
     out[0] = (uint32_t) g.ppw; out[1] = g.grid_x; out[2] = g.grid_y; out[3] = (uint32_t) g.log_up;
     for (int k = 0; k < 4; k++) out[4 + k] = g.tp.rows[k];
-    using Cfg = PassCfg<FieldM32, 1, 0, true, false>;  // the row rule does not depend on the configuration
+    using Cfg = ContigCfg<FieldM32, 1, false>;  // the row rule does not depend on the configuration
     PassArgs<Cfg> a;
     memset((void *) &a, 0, sizeof(a));
     a.ppw = g.ppw;

@@ -2,23 +2,14 @@
 //
 // TEST INFRASTRUCTURE, a sibling of emu.cpp: the same pass.h / plan.h / field.h the HIP kernels are built from, under g++, every
 // thread context of a workgroup stepped phase by phase, with the LDS hazard tracker on.  The first pass is the configuration
-// lde_dispatch() names -- the rule the launcher itself uses (pass_kernel.inc) -- and the column passes behind it are the plain
-// ones, so a whole low-degree extension runs here exactly as ntt_lde sequences it.
+// the launcher's own rule names (csrc/launch.h: pass_dispatch, lde_dispatch behind it), with the launcher's argument block, and the
+// column passes behind it are the plain ones, so a whole low-degree extension runs here exactly as ntt_lde sequences it.
 //   * as a library (tests/emu_lde_lib.py): emu_lde() on the caller's buffers;
 //   * with -DEMU_LDE_MAIN (tests/test_lde_emu_asan.py, built with ASan + UBSan and linked with oracle/ntt_oracle.c): a sweep over
 //     word classes x logM 5..17 x blow-up 1..4 x ragged batches x both layouts x every plan alternative on malloc() buffers of
 //     EXACTLY batch * N input words, batch * M output words and max(N, 4) coset words, each case compared with the oracle's
 //     network applied to the expanded input.
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
-#define NTT_EMU_TRACK 1
-#include "../../ntt_aie_amd/csrc/pass.h"
-#include "../../ntt_aie_amd/csrc/plan.h"
+#include "emu_exec.h"
 
 using namespace ntt;
 using namespace ntt::host;
@@ -31,153 +22,21 @@ using namespace ntt::host;
 
 namespace {
 
-// LDS hazard tracker, as in emu.cpp: a word may be read by a wave only if its last write is the wave's own or older than the
-// last workgroup barrier, and written only if every read since that barrier was the wave's own
-struct Track : ntt::LdsTrack {
-    struct St {
-        int w_wave = -1, w_epoch = -1, r_wave = -1, r_epoch = -1;
-    };
-    std::vector<St> st;
-    const char *base = nullptr;
-    size_t wb = 1;
-    int epoch = 0;
-    void reset(const void *tile, size_t words, size_t word_bytes) {
-        base = (const char *) tile;
-        wb = word_bytes;
-        st.assign(words, St());
-        epoch = 0;
-    }
-    void access(const void *word, uint32_t tid, bool write) override {
-        const int wave = (int) (tid >> 6);
-        const size_t idx = (size_t) ((const char *) word - base) / wb;
-        if ((const char *) word < base || idx >= st.size()) return;
-        St &s = st[idx];
-        const bool raw = s.w_epoch == epoch && s.w_wave != wave && s.w_wave != -1;
-        const bool war = write && s.r_epoch == epoch && s.r_wave != wave && s.r_wave != -1;
-        if (raw || war) {
-            fprintf(stderr, "LDS hazard: wave %d %s a word another wave touched since the last workgroup barrier\n", wave, write ? "writes" : "reads");
-            abort();
-        }
-        if (write) {
-            s.w_wave = wave;
-            s.w_epoch = epoch;
-        } else if (s.r_epoch == epoch && s.r_wave != wave) {
-            s.r_wave = -2;
-        } else {
-            s.r_wave = wave;
-            s.r_epoch = epoch;
-        }
-    }
-};
-
-template <class Cfg>
-struct Exec {
-    static constexpr bool early_ok = true;
-    std::vector<Ctx<Cfg>> ctx;
-    std::vector<typename Cfg::W> tile;
-    uint32_t bx = 0, by = 0;
-    Track tr;
-    Exec() : ctx(Cfg::NT), tile(Cfg::DMA ? 2 * Cfg::TILE_WORDS : Cfg::LDS_WORDS) {}
-    void init(const PassArgs<Cfg> &a) {
-        for (int t = 0; t < Cfg::NT; t++) phase_init<Cfg>(ctx[t], a, (uint32_t) t, bx, by);
-    }
-    void init_indices(const PassArgs<Cfg> &a) {
-        for (int t = 0; t < Cfg::NT; t++) phase_init<Cfg, false>(ctx[t], a, (uint32_t) t, bx, by);
-    }
-    template <class Fn>
-    void each(Fn &&f) {
-        for (int t = 0; t < Cfg::NT; t++) f(ctx[t]);
-    }
-    void sync(std::false_type) { ++tr.epoch; }
-    void sync(std::true_type) {}
-    uint32_t pg_base() const { return ctx[0].pg_base; }
-    int ppw() const { return ctx[0].ppw; }
-    bool iter_begin(int) { return true; }
-    void iter_done(int) {}
-    void pass_done(int) {}
-    typename Cfg::W *lds() { return tile.data(); }
-};
-
-struct Job {
-    int wb, logn, beta, layout;
-    uint64_t p;
-    uint32_t batch, target_wgs;
-    const void *tw;   // size-M forward table, table form
-    const void *sv;   // coset vector, table form, max(N, 4) words
-    const void *in;   // [batch][N]
-    void *out;        // [batch][M]
-};
-
+// the passes of one plan alternative, as ntt_lde sequences them: the first one with the coset operand, the others in place on e.out;
+// every kernel is the one the GPU launcher's rule names (csrc/launch.h: pass_dispatch)
 template <class F>
-F field_of(const Job &j);
-template <>
-FieldGL field_of<FieldGL>(const Job &) {
-    return FieldGL{};
-}
-template <>
-FieldM32 field_of<FieldM32>(const Job &j) {
-    return FieldM32{(uint32_t) j.p, mont_pinv((uint32_t) j.p), mont_r2((uint32_t) j.p)};
-}
-template <>
-FieldM64 field_of<FieldM64>(const Job &j) {
-    return FieldM64{j.p, mont_pinv64(j.p), mont_r2_64(j.p)};
-}
-
-template <class Cfg>
-void run_one(const Job &j, const PassDesc &pd, bool lde) {
-    using W = typename Cfg::W;
-    PassArgs<Cfg> a;
-    memset((void *) &a, 0, sizeof(a));
-    a.in = lde ? nullptr : (const W *) j.out;  // the fused pass must not read `in` at all
-    a.out = (W *) j.out;
-    a.tw = (const W *) j.tw;
-    a.field = field_of<typename Cfg::F>(j);
-    a.n = j.logn;
-    a.s0 = pd.s0;
-    a.batch = j.batch;
-    a.layout = j.layout;
-    a.pg_stride = 1;
-    if (lde) {
-        a.lde_in = (const W *) j.in;
-        a.lde_s = (const W *) j.sv;
-        a.lde_beta = j.beta;
-    }
-    const PassGeom g = pass_geometry(j.logn, pd.s0, Cfg::LOG_M, Cfg::LOG_C, Cfg::LOG_U, Cfg::CONTIG, j.batch, j.target_wgs, Cfg::PPW_CAP);
-    a.ppw = g.ppw;
-    a.tp = g.tp;
-    a.log_ul = g.log_ul;
-    a.log_uh = g.log_uh;
-    a.log_up = g.log_up;
-    Exec<Cfg> ex;
-    for (uint32_t by = 0; by < g.grid_y; by++)
-        for (uint32_t bx = 0; bx < g.grid_x; bx++) {
-            ex.bx = bx;
-            ex.by = by;
-            memset(ex.tile.data(), 0xA5, ex.tile.size() * sizeof(W));  // a word nobody wrote shows up as garbage
-            ex.tr.reset(ex.tile.data(), ex.tile.size(), sizeof(W));
-            ntt::lds_track() = &ex.tr;
-            run_pass<Cfg>(ex, a);
-            ntt::lds_track() = nullptr;
-        }
-}
-
-template <class F>
-int run_lde(const Job &j, const std::vector<PassDesc> &passes) {
+int run_lde(ErasedArgs e, const void *in, const void *sv, int beta, const std::vector<PassDesc> &passes) {
     for (const PassDesc &pd : passes) {
-        if (&pd == &passes.front()) {
-            if (!pd.contig || pd.s0 != 0) return -1;
-            if (!lde_dispatch<F>(pd.log_m, pd.log_m == j.logn, [&](auto tag) { run_one<typename decltype(tag)::Cfg>(j, pd, true); })) return -2;
-            continue;
-        }
-        switch (pd.log_m) {
-            case 4: run_one<ColPassCfg<F, 4, false>>(j, pd, false); break;
-            case 5: run_one<ColPassCfg<F, 5, false>>(j, pd, false); break;
-            case 6: run_one<ColPassCfg<F, 6, false>>(j, pd, false); break;
-            case 7: run_one<ColPassCfg<F, 7, false>>(j, pd, false); break;
-            case 8: run_one<ColPassCfg<F, 8, false>>(j, pd, false); break;
-            case 9: run_one<ColPassCfg<F, 9, false>>(j, pd, false); break;
-            default: return -3;
-        }
+        const bool first = &pd == &passes.front();
+        if (first && (!pd.contig || pd.s0 != 0)) return -1;
+        e.s0 = pd.s0;
+        e.in = first ? nullptr : e.out;  // the fused pass must not read `in` at all
+        e.lde_in = first ? in : nullptr;
+        e.lde_s = first ? sv : nullptr;
+        e.lde_beta = first ? beta : 0;
+        int rc = first ? -2 : -3;  // no such kernel
+        pass_dispatch<F, false>(pd.contig, pd.log_m, e, [&](auto tag) { rc = emu::run_pass_launch<typename decltype(tag)::Cfg>(e, true); });
+        if (rc) return rc;
     }
     return 0;
 }
@@ -213,17 +72,25 @@ int emu_lde(int word_bytes, int logn, uint64_t p, const void *T_plain, int beta,
     const int k = alt >= 0 ? alt : select_alternative(alts, batch);
     int rc = -4;
     if (k < (int) alts.size()) {
-        const Job j{word_bytes, logn, beta, layout, p, batch, target_wgs, tw, sv, in, out};
+        ErasedArgs e;
+        memset(&e, 0, sizeof(e));
+        e.field = field_params(word_bytes, p);
+        e.out = out;
+        e.tw = tw;
+        e.n = logn;
+        e.batch = batch;
+        e.layout = layout;
+        e.target_wgs = target_wgs;
         const std::vector<PassDesc> &passes = alts[(size_t) k].passes;
         rc = -100;
 #if EMU_LDE_FIELDS & 1
-        if (word_bytes == 8 && p == GOLDILOCKS) rc = run_lde<FieldGL>(j, passes);
+        if (e.field.kind == FK_GL) rc = run_lde<FieldGL>(e, in, sv, beta, passes);
 #endif
 #if EMU_LDE_FIELDS & 2
-        if (word_bytes == 8 && p != GOLDILOCKS) rc = run_lde<FieldM64>(j, passes);
+        if (e.field.kind == FK_M64) rc = run_lde<FieldM64>(e, in, sv, beta, passes);
 #endif
 #if EMU_LDE_FIELDS & 4
-        if (word_bytes == 4) rc = run_lde<FieldM32>(j, passes);
+        if (e.field.kind == FK_M32) rc = run_lde<FieldM32>(e, in, sv, beta, passes);
 #endif
     }
     free(tw);

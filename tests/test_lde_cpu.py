@@ -134,7 +134,8 @@ def test_lde_error_contract_without_a_device():
 
 def test_fused_expansion_is_never_a_dma_or_prefetch_kernel():
     """the rule is in the configuration type, and the launcher refuses a mismatch: PassCfg::DMA and ::PREFETCH both carry !LDE_,
-    launch_cfg returns an error when the coset operand meets a kernel that is not its own (and the other way round)"""
+    launch_cfg returns an error when the coset operand meets a kernel that is not its own (and the other way round); the shared
+    argument fill behind it (launch.h: fill_pass_args, also the host model's) refuses the same mismatch"""
     src = open(os.path.join(ROOT, "ntt_aie_amd", "csrc", "pass.h")).read()
     assert re.search(r"static constexpr bool DMA = ALLOW_DMA_ && !LDE_ &&", src)
     assert re.search(r"static constexpr bool PREFETCH = NTT_PREFETCH_M32_WIDE && ALLOW_DMA_ && !LDE_ &&", src)
