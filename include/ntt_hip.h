@@ -126,7 +126,9 @@ int ntt_plan_get_twiddles(ntt_plan_t plan, int inverse, void *host_T);
  * 512 + 16*a + k: the kernel variant of pass k of alternative a (0 = the default kernel of that pass shape; 1 = a single-pass
  * size of 2^10..2^12 words on twice the threads, chosen below the batch that fills the device);
  * 9 the coset blow-up log2 set by ntt_plan_set_coset (0 = not set), 10 whether ntt_lde on this plan expands inside its first
- * pass (1) or runs the separate expansion kernel first (0; also 0 while no coset is set) */
+ * pass (1) or runs the separate expansion kernel first (0; also 0 while no coset is set);
+ * 11 whether a coset-inverse shift is set (ntt_plan_set_coset_inverse), 12 whether ntt_coset_inverse on this plan scales inside
+ * its last pass (1) or runs the separate row-scaling kernel after the transform (0; also 0 while nothing is set) */
 int64_t ntt_plan_info(ntt_plan_t plan, int what);
 
 /* The stage decomposition into HBM passes is chosen at LAUNCH, by batch size, among alternatives fixed at plan creation
@@ -184,6 +186,33 @@ int ntt_forward(ntt_plan_t plan, const void *d_in, void *d_out, size_t batch,
  * batch == 0 is NTT_OK. */
 int ntt_plan_set_coset(ntt_plan_t plan, int log_blowup, uint64_t shift);
 int ntt_lde(ntt_plan_t plan, const void *d_in, void *d_out, size_t batch, int out_layout, void *stream);
+
+/* ---- coset interpolation (no reference counterpart) ---------------------------
+ * The other half of a prover round: from values on the coset shift * <w_M>, M = 2^logn of this plan, back to coefficients
+ * -- the "coset iFFT", an inverse transform followed by coeff[i] *= shift^-i, as ONE call.
+ *
+ * ntt_plan_set_coset_inverse: plan configuration under the rules of ntt_plan_set_coset (before the plan is shared between
+ * host threads; a second call replaces the setting).  Independent of ntt_plan_set_coset: no blow-up, and neither call touches
+ * the other's setting or vector.  shift in [1, p), else NTT_E_ARG; a shift that shares a factor with a composite p returns
+ * NTT_E_NOTINVERTIBLE.  Builds on the device (no host table) the plan-owned vector of M words
+ * u[i] = shift^(-bitrev_logM(i)) * M^-1 mod p in the arithmetic's table form: one more table's worth of device memory,
+ * decomposition-agnostic like the tables.  ntt_plan_clone copies the setting and the vector device-to-device;
+ * ntt_forward / ntt_inverse / ntt_lde on the plan are unaffected.
+ *
+ * ntt_coset_inverse: defined at network level, hence for any invertible table:
+ *     d_out[b][i] = InvScaled_M(d_in[b])[i] * shift^(-bitrev_logM(i)) mod p,
+ * InvScaled_M = exactly what ntt_inverse(..., scale = 1) computes.  d_in is in `in_layout`, d_out in natural order;
+ * d_in == d_out allowed, as for ntt_inverse.  With kind-1 tables and d_in[b][k] = P_b(shift * w_M^k), d_out[b][i] is
+ * coefficient bitrev_M(i) of P_b: the order ntt_lde consumes, still no bit-reversal pass anywhere ("LDE").
+ * Asynchronous on `stream`; no allocation, no host synchronisation; the decomposition is the one ntt_plan_select(plan, batch)
+ * names, a pinned policy is honoured.  From logn = 5 on, the inverse's last pass (the contiguous one, stages .. 0) multiplies
+ * every output word by its word of u just before the store, where the scaled inverse multiplies by M^-1: no HBM traffic
+ * beyond ntt_inverse's own.  Smaller sizes run the unscaled inverse and then a row-scaling kernel (ntt_plan_info 12).
+ * No access outside the caller's batch * M words of each buffer; the vector read never leaves its M words.
+ * Errors: NTT_E_ARG for a null or misaligned pointer, batch out of range, a bad layout or no coset-inverse shift set;
+ * NTT_E_NOTABLE / NTT_E_NOTINVERTIBLE / NTT_E_LAYOUT as ntt_inverse.  batch == 0 is NTT_OK. */
+int ntt_plan_set_coset_inverse(ntt_plan_t plan, uint64_t shift);
+int ntt_coset_inverse(ntt_plan_t plan, const void *d_in, void *d_out, size_t batch, int in_layout, void *stream);
 
 /* Profiling twin of ntt_forward (the reference brackets one kernel iteration with
  * trace events, src/aie_core.cc:129-131, src/aie2.py:168,316): identical launches

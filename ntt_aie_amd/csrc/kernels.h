@@ -47,10 +47,13 @@ hipError_t launch_fused_gl16(const void *in, void *out, const void *tw, size_t b
 hipError_t launch_pointwise(const FieldParams &fp, const void *a, const void *b, void *c, size_t count, uint64_t scale, hipStream_t s);
 // device-side table generation (no host upload): T[i] = base^e_kind(i), table form
 hipError_t launch_gen_table(const FieldParams &fp, void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, hipStream_t s);
-// coset vector of ntt_plan_set_coset: s[i] = shift^bitrev_logn(i mod 2^logn), table form, i < len (len = max(2^logn, 4))
+// coset vector of ntt_plan_set_coset: s[i] = shift^bitrev_logn(i mod 2^logn), table form, i < len (len = max(2^logn, 4));
+// one_m = the table form of a constant c instead of 1: s[i] * c (ntt_plan_set_coset_inverse: shift^-1 and c = N^-1)
 hipError_t launch_gen_coset(const FieldParams &fp, void *s_out, int logn, uint32_t len, uint64_t shift_m, uint64_t one_m, hipStream_t s);
 // the separate expansion of ntt_lde: out[b][i << beta] = in[b][i] * s[i], zeros between; in: [batch][2^(n - beta)], out: [batch][2^n] words
 hipError_t launch_lde_expand(const FieldParams &fp, const void *in, const void *s_vec, void *out, int n, int beta, size_t batch, hipStream_t s);
+// the separate scaling of ntt_coset_inverse, in place: buf[b][i] *= u[i]; buf: [batch][2^n] words, u: max(2^n, 4) words, table form
+hipError_t launch_row_scale(const FieldParams &fp, void *buf, const void *u_vec, int n, size_t batch, hipStream_t s);
 // out[i] = T[i] * c (table form both): the N/2 scaled stage-0 twiddles of the inverse transform (8-byte words only)
 hipError_t launch_scale_table(const FieldParams &fp, const void *T, void *out, size_t count, uint64_t c_m, hipStream_t s);
 // number of words >= p in a buffer (precondition check); d_out = one zeroed 64-bit device word

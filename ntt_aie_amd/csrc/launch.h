@@ -60,6 +60,7 @@ struct ErasedArgs {
     const void *lde_in;   // forward CONTIG first pass of ntt_lde: compact source / coset vector / log2 blow-up (PassArgs::lde_*);
     const void *lde_s;    // lde_beta == 0: an ordinary launch
     int lde_beta;
+    const void *cinv_u;   // inverse CONTIG pass of ntt_coset_inverse: the per-position output vector (PassArgs::cinv_u); null: an ordinary launch
 #if defined(NTT_PHASE_STAMPS)
     void *stamps;            // diagnostic build: PassArgs::stamps / stamp_records (ntt_stamps_set)
     uint32_t stamp_records;
@@ -67,23 +68,24 @@ struct ErasedArgs {
 };
 
 // ---- the pass kernels of one (field, direction) ------------------------------------------------------------------
-template <class F, int LOG_M, bool INV>
-using ContigCfg = PassCfg<F, LOG_M, 0, true, INV, contig_preload_mask(LOG_M, sizeof(typename F::W))>;
+// (CINV: the coset-interpolation twin of an inverse kernel, PassCfg::CINV -- the same shape with the vector sweep at its end)
+template <class F, int LOG_M, bool INV, bool CINV = false>
+using ContigCfg = PassCfg<F, LOG_M, 0, true, INV, contig_preload_mask(LOG_M, sizeof(typename F::W)), 4, LOG_NT, true, false, CINV>;
 // 13 stages on an 8192-word tile: 512 threads x 16 words, rounds of 4 + 4 + 4 + 1 stages.  4-byte words keep every round's
 // twiddles in registers (99 VGPRs); 8-byte words only the last round's single, wave-uniform one (the others are re-read
 // from L2 at the start of their round, as in the 12-stage radix-16 pass: 128 VGPRs, two workgroups per CU)
-template <class F, bool INV>
-using ContigCfg13 = PassCfg<F, 13, 0, true, INV, sizeof(typename F::W) == 4 ? 0xF : 0x8, 4, 9>;
+template <class F, bool INV, bool CINV = false>
+using ContigCfg13 = PassCfg<F, 13, 0, true, INV, sizeof(typename F::W) == 4 ? 0xF : 0x8, 4, 9, true, false, CINV>;
 // 14 stages on a 16384-word tile of 4-byte words (64 KiB): ONE 1024-thread workgroup per CU, rounds of 4 + 4 + 4 + 2 stages, every
 // round's twiddles resident.  Pays only for the lazy butterflies (p < 2^30: N = 2^14 in one pass -21 % forward, -5 % inverse at
 // saturating batches; +3 % for a 32-bit prime, +20 % for one polynomial: profiles/r02_ab_13_stage_pass.txt), so the planner offers it
 // as a launch-time alternative for that modulus class above a batch threshold (plan.h: plan_alternatives)
-template <class F, bool INV>
-using ContigCfg14 = PassCfg<F, 14, 0, true, INV, 0xF, 4, 10>;
+template <class F, bool INV, bool CINV = false>
+using ContigCfg14 = PassCfg<F, 14, 0, true, INV, 0xF, 4, 10, true, false, CINV>;
 // radix-8 rounds: 256 threads up to 9 stages, 512 threads for 10..12.  ALLOW_DMA = false: the same kernel with the tile staged
 // by ordinary loads, which is where a fused pointwise product (a.in2) has room to multiply
-template <class F, int LOG_M, bool INV, bool ALLOW_DMA = true>
-using ContigCfgE8 = PassCfg<F, LOG_M, 0, true, INV, 0xF, 3, LOG_M >= 10 ? 9 : 8, ALLOW_DMA>;
+template <class F, int LOG_M, bool INV, bool ALLOW_DMA = true, bool CINV = false>
+using ContigCfgE8 = PassCfg<F, LOG_M, 0, true, INV, 0xF, 3, LOG_M >= 10 ? 9 : 8, ALLOW_DMA, false, CINV>;
 
 // fn(std::integral_constant<int, M>{}) for the M in [LO, HI] that equals log_m; false = none does
 template <int LO, int HI, class Fn>
@@ -97,41 +99,55 @@ bool with_log_m(int log_m, Fn &&fn) {
     }
 }
 
-// THE selection rule: fn(CfgTag<Cfg>{}) with the configuration of the pass kernel that runs stages [a.s0, a.s0 + log_m) of
-// this launch; false = no such kernel.
-template <class F, bool INV, class Fn>
-bool pass_dispatch(bool contig, int log_m, const ErasedArgs &a, Fn &&fn) {
+// The CONTIG kernel of 2^log_m words for this launch.  CINV: its coset-interpolation twin (inverse only) -- the SAME shape rule, so
+// ntt_coset_inverse's last pass is the kernel ntt_inverse would run there plus the vector sweep; twins exist where the pass has two
+// register rounds or more (log_m >= 5: every radix-8 shape, 13, 14 of 4-byte words -- the family lde_dispatch covers forward).
+constexpr int CINV_MIN_LOG_M = 5;
+template <class F, bool INV, bool CINV, class Fn>
+bool contig_dispatch(int log_m, const ErasedArgs &a, bool last_pass, Fn &&fn) {
+    static_assert(INV || !CINV, "coset interpolation ends an INVERSE transform");
     constexpr int WB = (int) sizeof(typename F::W);
-    const bool last_pass = a.s0 + log_m == a.n;
-    if (a.lde_beta != 0) {  // first pass of ntt_lde: the fused-expansion twin of this shape (pass.h: lde_dispatch)
-        if constexpr (INV) return false;
-        else return contig && lde_dispatch<F>(log_m, last_pass, fn);
-    }
-    if (!contig)  // 9: 512 rows x one 128-byte segment: N = 2^22 = 13 + 9 in two passes
-        return with_log_m<4, 9>(log_m, [&](auto m) { fn(CfgTag<ColPassCfg<F, decltype(m)::value, INV>>{}); });
     if (log_m == 13) {
-        fn(CfgTag<ContigCfg13<F, INV>>{});
+        fn(CfgTag<ContigCfg13<F, INV, CINV>>{});
         return true;
     }
     if (log_m == 14) {
-        if constexpr (WB == 4) fn(CfgTag<ContigCfg14<F, INV>>{});
+        if constexpr (WB == 4) fn(CfgTag<ContigCfg14<F, INV, CINV>>{});
         return WB == 4;
     }
     // PassDesc::variant 1: a single-pass unit of 2^10 .. 2^12 words on 512 threads x 8 words (radix-8 rounds; 8-byte forward: the
     // LDS-DMA kernel that otherwise runs as the first pass of a two-pass plan) instead of 256 x 16 -- twice the waves for the same
     // work, for launches too small to fill the SIMDs (plan.h: plan_alternatives).  Both layouts (pass.h: elem_off / lane_eff);
     // a fused pointwise operand keeps the default kernel.
-    if (a.variant == 1 && a.in2 == nullptr && with_log_m<10, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfgE8<F, decltype(m)::value, INV>>{}); }))
+    if (a.variant == 1 && a.in2 == nullptr && with_log_m<10, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfgE8<F, decltype(m)::value, INV, true, CINV>>{}); }))
         return true;
     if constexpr (WB == 8) {
         if (contig_log_e(log_m, WB, last_pass) == 3) {
             if constexpr (!INV) {  // fused pointwise product: the twins without LDS-DMA
                 if (a.in2 != nullptr) return with_log_m<7, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfgE8<F, decltype(m)::value, INV, false>>{}); });
             }
-            return with_log_m<7, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfgE8<F, decltype(m)::value, INV>>{}); });
+            return with_log_m<7, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfgE8<F, decltype(m)::value, INV, true, CINV>>{}); });
         }
     }
-    return with_log_m<1, 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfg<F, decltype(m)::value, INV>>{}); });
+    return with_log_m<(CINV ? CINV_MIN_LOG_M : 1), 12>(log_m, [&](auto m) { fn(CfgTag<ContigCfg<F, decltype(m)::value, INV, CINV>>{}); });
+}
+
+// THE selection rule: fn(CfgTag<Cfg>{}) with the configuration of the pass kernel that runs stages [a.s0, a.s0 + log_m) of
+// this launch; false = no such kernel.
+template <class F, bool INV, class Fn>
+bool pass_dispatch(bool contig, int log_m, const ErasedArgs &a, Fn &&fn) {
+    const bool last_pass = a.s0 + log_m == a.n;
+    if (a.lde_beta != 0) {  // first pass of ntt_lde: the fused-expansion twin of this shape (pass.h: lde_dispatch)
+        if constexpr (INV) return false;
+        else return contig && a.cinv_u == nullptr && lde_dispatch<F>(log_m, last_pass, fn);
+    }
+    if (a.cinv_u != nullptr) {  // last executed pass of ntt_coset_inverse: the twin with the vector sweep
+        if constexpr (INV) return contig && contig_dispatch<F, true, true>(log_m, a, last_pass, fn);
+        else return false;
+    }
+    if (!contig)  // 9: 512 rows x one 128-byte segment: N = 2^22 = 13 + 9 in two passes
+        return with_log_m<4, 9>(log_m, [&](auto m) { fn(CfgTag<ColPassCfg<F, decltype(m)::value, INV>>{}); });
+    return contig_dispatch<F, INV, false>(log_m, a, last_pass, fn);
 }
 
 template <class Cfg>
@@ -172,6 +188,13 @@ bool fill_pass_args(const ErasedArgs &e, const PassGeom &g, PassArgs<Cfg> &a) {
         a.lde_in = (const W *) e.lde_in;
         a.lde_s = (const W *) e.lde_s;
         a.lde_beta = e.lde_beta;
+    }
+    // ... and so does the vector sweep of a coset interpolation (PassCfg::CINV): refused on any other configuration, and a twin
+    // is refused without its vector; N^-1 is inside the vector, so such a launch is never a scaled one
+    if ((e.cinv_u != nullptr) != Cfg::CINV) return false;
+    if constexpr (Cfg::CINV) {
+        if (e.s0 != 0 || e.do_scale || e.tw_sc || e.in2) return false;
+        a.cinv_u = (const W *) e.cinv_u;
     }
     if constexpr (fold_scale<Cfg>()) {
         if (e.do_scale && e.tw_sc == nullptr) return false;  // these kernels have no scaling sweep

@@ -180,6 +180,31 @@ __global__ __launch_bounds__(256) void lde_expand_kernel(const typename F::W *in
     }
 }
 
+// The separate scaling of ntt_coset_inverse (sizes whose last pass has no twin with the vector sweep; that sweep's comparator):
+// buf[b][i] = buf[b][i] * u[i] in place, one thread per 16-byte chunk of the [batch][2^n] buffer, grid-stride.  A row of 2^n words
+// is a whole number of chunks or (n = 1, 4-byte words) half of one: the vector is then stored periodically up to one chunk, so a
+// chunk's multipliers are always the aligned chunk (word & u_mask) of it.  Canonical words in, canonical words out.
+template <class F>
+__global__ __launch_bounds__(256) void row_scale_kernel(typename F::W *buf, const typename F::W *u, size_t count, uint32_t u_mask, F f) {
+    using W = typename F::W;
+    constexpr int V = 16 / sizeof(W);
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    const size_t chunks = count / V, stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t c = (size_t) blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += stride) {
+        const u32x4 xx = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(buf) + c);
+        const Vec<W, V> m = *reinterpret_cast<const Vec<W, V> *>(u + ((uint32_t) (c * V) & u_mask));
+        Vec<W, V> x;
+        __builtin_memcpy(&x, &xx, 16);
+#pragma unroll
+        for (int k = 0; k < V; ++k) x.v[k] = f.mul(x.v[k], m.v[k]);
+        u32x4 zz;
+        __builtin_memcpy(&zz, &x, 16);
+        __builtin_nontemporal_store(zz, reinterpret_cast<u32x4 *>(buf) + c);
+    }
+    // tail (count not a multiple of V: only N = 2 with 4-byte words and an odd batch)
+    for (size_t i = chunks * V + (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) buf[i] = f.mul(buf[i], u[(uint32_t) i & u_mask]);
+}
+
 // out[i] = T[i] * c, both in table (Montgomery) form: the scaled stage-0 twiddles of the inverse transform (pass.h: fold_scale)
 template <class F>
 __global__ __launch_bounds__(256) void scale_table_kernel(const typename F::W *T, typename F::W *out, size_t count,
@@ -256,6 +281,20 @@ hipError_t launch_lde_expand(const FieldParams &fp, const void *in, const void *
         using F = decltype(f);
         using W = typename F::W;
         hipLaunchKernelGGL(lde_expand_kernel<F>, dim3(grid_for(chunks)), dim3(256), 0, s, (const W *) in, (const W *) s_vec, (W *) out, chunks, n, beta, f);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_row_scale(const FieldParams &fp, void *buf, const void *u_vec, int n, size_t batch, hipStream_t s) {
+    const size_t count = batch << n;
+    if (count == 0) return hipSuccess;
+    const size_t u_words = ((size_t) 1 << n) < 4 ? 4 : (size_t) 1 << n;  // the vector's (periodic) length, a power of two
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        using W = typename F::W;
+        // (grid_for caps the grid far below the launch limits and the kernel strides over a 64-bit count: no slicing needed)
+        hipLaunchKernelGGL(row_scale_kernel<F>, dim3(grid_for((count + 16 / sizeof(W) - 1) / (16 / sizeof(W)))), dim3(256), 0, s, (W *) buf, (const W *) u_vec, count,
+                           (uint32_t) (u_words - 1), f);
         return hipGetLastError();
     });
 }

@@ -109,6 +109,11 @@ struct ntt_plan {
     uint64_t lde_shift = 0;
     void *d_lde_s = nullptr;  // s[i] = shift^bitrev(i), table form, max(N >> lde_beta, 4) words (misc_kernels.hip: gen_coset_kernel)
     int lde_unfused = 0;      // experiment build only (NTT_LDE_UNFUSED=1): ntt_lde takes the separate expansion kernel at every size; 0 in the product
+    // ntt_plan_set_coset_inverse: interpolation from shift * <w_N> (independent of the setting above)
+    bool cinv_set = false;
+    uint64_t cinv_shift = 0;
+    void *d_cinv_u = nullptr;  // u[i] = shift^-bitrev(i) * N^-1, table form, max(N, 4) words (gen_coset_kernel with shift^-1 and the constant N^-1)
+    int cinv_unfused = 0;      // experiment build only (NTT_COSET_INV_UNFUSED=1): ntt_coset_inverse takes the separate row-scaling kernel at every size; 0 in the product
 };
 
 static_assert(NTT_E_NOMEM == NTT_E_NOMEM_GUARD && NTT_E_INTERNAL == NTT_E_INTERNAL_GUARD, "guard.h codes = include/ntt_hip.h codes");
@@ -124,6 +129,7 @@ void free_plan(ntt_plan *pl) {
     if (pl->d_fused_ctl) (void) hipFree(pl->d_fused_ctl);
     if (pl->d_counter) (void) hipFree(pl->d_counter);
     if (pl->d_lde_s) (void) hipFree(pl->d_lde_s);
+    if (pl->d_cinv_u) (void) hipFree(pl->d_cinv_u);
     delete pl;
 }
 // ntt_plan_create builds the plan under this holder: an exception (std::bad_alloc from the alternatives' vectors)
@@ -146,6 +152,34 @@ size_t lde_s_words(const ntt_plan *pl, int beta) {
 }
 // does ntt_lde expand inside the first pass of this plan (every alternative's first pass has >= 5 stages from logn = 5 on)
 bool lde_fused(const ntt_plan *pl) { return pl->lde_beta > 0 && pl->logn >= ntt::LDE_MIN_LOG_M && !pl->lde_unfused; }
+
+// words of the coset-interpolation vector (periodic up to one 16-byte chunk of 4-byte words, like the coset vector)
+size_t cinv_u_words(const ntt_plan *pl) {
+    const size_t n = (size_t) 1 << pl->logn;
+    return n < 4 ? 4 : n;
+}
+// does the inverse CONTIG pass of this decomposition have a twin with the vector sweep (launch.h: pass_dispatch is the rule)
+bool cinv_pass_fused(const ntt_plan *pl, const std::vector<PassDesc> &passes) {
+    if (pl->cinv_unfused || passes.empty() || !passes[0].contig || passes[0].s0 != 0) return false;
+    ntt::ErasedArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = pl->logn;
+    a.variant = passes[0].variant;
+#if defined(NTT_EXPERIMENT)
+    if (pl->force_variant >= 0) a.variant = pl->force_variant;  // as base_args: the question is about the kernel that will be launched
+#endif
+    static const char selection_only = 0;  // stands for "a vector is present": nothing is launched, only the selection is asked for
+    a.cinv_u = &selection_only;
+    return ntt::with_field(pl->field, [&](auto f) { return ntt::pass_dispatch<decltype(f), true>(true, passes[0].log_m, a, [](auto) {}); });
+}
+// ntt_plan_info 12: ntt_coset_inverse scales inside its last pass whatever the batch (every alternative, or the pinned one)
+bool cinv_fused(const ntt_plan *pl) {
+    if (!pl->cinv_set) return false;
+    if (pl->forced_alt >= 0) return cinv_pass_fused(pl, pl->alts[(size_t) pl->forced_alt].passes);
+    for (const PlanAlt &alt : pl->alts)
+        if (!cinv_pass_fused(pl, alt.passes)) return false;
+    return true;
+}
 
 // the decomposition the launchers run for this batch
 const std::vector<PassDesc> &passes_for(const ntt_plan *pl, size_t batch) {
@@ -372,6 +406,7 @@ int ntt_plan_create(ntt_plan_t *out, int logn, uint64_t p, int word_bytes, int d
     if (const char *e = getenv("NTT_PASS_VARIANT")) pl->force_variant = atoi(e);
     if (const char *e = getenv("NTT_FUSED")) pl->fused = atoi(e);
     if (const char *e = getenv("NTT_LDE_UNFUSED")) pl->lde_unfused = atoi(e) != 0;  // tools/bench_lde.py: leg B
+    if (const char *e = getenv("NTT_COSET_INV_UNFUSED")) pl->cinv_unfused = atoi(e) != 0;  // tools/bench_coset_inverse.py: leg B
     if (const char *e = getenv("NTT_PLAN_SPLIT")) {  // "8,6,6" = CONTIG 8 stages + two 6-stage column passes
         std::vector<PassDesc> v;
         int s0 = 0;
@@ -530,6 +565,8 @@ int64_t ntt_plan_info(ntt_plan_t pl, int what) NTT_GUARD {
         case 7: return pl->forced_alt;
         case 9: return pl->lde_beta;
         case 10: return lde_fused(pl) ? 1 : 0;
+        case 11: return pl->cinv_set ? 1 : 0;
+        case 12: return cinv_fused(pl) ? 1 : 0;
         case 8: {  // capacity for ntt_forward_profile whatever the batch
             size_t k = 0;
             for (const PlanAlt &a : pl->alts) k = a.passes.size() > k ? a.passes.size() : k;
@@ -600,6 +637,31 @@ int ntt_plan_set_coset(ntt_plan_t pl, int log_blowup, uint64_t shift) NTT_GUARD 
     return NTT_OK;
 } NTT_GUARD_END
 
+int ntt_plan_set_coset_inverse(ntt_plan_t pl, uint64_t shift) NTT_GUARD {
+    if (!pl) return NTT_E_ARG;
+    if (shift == 0 || shift >= pl->p) return NTT_E_ARG;
+    const uint64_t shift_inv = invmod(shift, pl->p);
+    if (shift_inv == 0) return NTT_E_NOTINVERTIBLE;  // shares a factor with a composite modulus
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    const size_t words = cinv_u_words(pl);
+    void *d_u = nullptr;
+    hipError_t e = hipMalloc(&d_u, words * (size_t) pl->word_bytes);
+    if (e != hipSuccess) return (int) e;
+    // u[i] = (shift^-1)^bitrev(i) * N^-1: the coset generator, started from the table form of N^-1 instead of 1
+    e = ntt::launch_gen_coset(pl->field, d_u, pl->logn, (uint32_t) words, to_table_form(shift_inv, pl->p, pl->word_bytes), pl->scale_tf, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void) hipFree(d_u);
+        return (int) e;
+    }
+    if (pl->d_cinv_u) (void) hipFree(pl->d_cinv_u);  // a replaced setting (configuration call: nothing is in flight on this plan)
+    pl->d_cinv_u = d_u;
+    pl->cinv_set = true;
+    pl->cinv_shift = shift;
+    return NTT_OK;
+} NTT_GUARD_END
+
 int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
     if (!out) return NTT_E_ARG;
     *out = nullptr;
@@ -642,6 +704,21 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
         }
         pl->lde_beta = src->lde_beta;
         pl->lde_shift = src->lde_shift;
+    }
+    pl->cinv_unfused = src->cinv_unfused;
+    if (src->cinv_set) {  // ... and the coset-interpolation setting with its vector
+        const size_t bytes = cinv_u_words(src) * (size_t) src->word_bytes;
+        DeviceGuard g(device);
+        hipError_t e = g.err;
+        if (e == hipSuccess) e = hipMalloc(&pl->d_cinv_u, bytes);
+        if (e == hipSuccess) e = copy_d2d(pl->d_cinv_u, device, src->d_cinv_u, src->device, bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            (void) ntt_plan_destroy(pl);
+            return (int) e;
+        }
+        pl->cinv_set = true;
+        pl->cinv_shift = src->cinv_shift;
     }
     *out = pl;
     return NTT_OK;
@@ -738,6 +815,31 @@ int ntt_inverse(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int 
     DeviceGuard g(pl->device);
     if (g.err != hipSuccess) return (int) g.err;
     return run_inverse(pl, d_in, d_out, batch, in_layout, scale, (hipStream_t) stream);
+} NTT_GUARD_END
+
+int ntt_coset_inverse(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int in_layout, void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_in, d_out, batch);
+    if (rc) return rc;
+    if (!pl->has_table) return NTT_E_NOTABLE;
+    if (!pl->has_inv) return NTT_E_NOTINVERTIBLE;
+    if (!pl->cinv_set) return NTT_E_ARG;
+    if ((rc = check_layout(pl, in_layout)) != NTT_OK) return rc;
+    if (batch == 0) return NTT_OK;
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    hipStream_t s = (hipStream_t) stream;
+    RoctxRange whole("ntt_coset_inverse");
+    const std::vector<PassDesc> &passes = passes_for(pl, batch);
+    if (!cinv_pass_fused(pl, passes)) {
+        // the unscaled inverse, then the scaling as a launch of its own, in place on the output
+        rc = run_inverse(pl, d_in, d_out, batch, in_layout, 0, s, &passes);
+        if (rc) return rc;
+        return (int) ntt::launch_row_scale(pl->field, d_out, pl->d_cinv_u, pl->logn, batch, s);
+    }
+    // the passes of the unscaled inverse; the last one launched (the CONTIG pass) multiplies by the vector before it stores
+    return run_passes(pl, passes, 0, passes.size(), true, "coset inv pass", d_in, d_out, batch, in_layout, s, [&](ntt::ErasedArgs &a, size_t i) {
+        if (i == 0) a.cinv_u = pl->d_cinv_u;
+    });
 } NTT_GUARD_END
 
 int ntt_pointwise_mul(ntt_plan_t pl, const void *d_a, const void *d_b, void *d_out, size_t batch,

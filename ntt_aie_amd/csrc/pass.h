@@ -117,7 +117,7 @@ NTT_HD void static_for(Fn &&f) {
 }
 
 template <class F_, int LOG_M_, int LOG_C_, bool CONTIG_, bool INV_, int PRELOAD_MASK_ = 0xF, int LOG_E_ = 4,
-          int LOG_NT_ = LOG_NT, bool ALLOW_DMA_ = true, bool LDE_ = false>
+          int LOG_NT_ = LOG_NT, bool ALLOW_DMA_ = true, bool LDE_ = false, bool CINV_ = false>
 struct PassCfg {
     using F = F_;
     using W = typename F::W;
@@ -192,6 +192,11 @@ struct PassCfg {
     // never an LDS-DMA or a register-prefetch kernel, whatever its shape -- the rule is here, not in a launcher's habits.
     static constexpr bool LDE = LDE_;
     static_assert(!LDE_ || (CONTIG_ && !INV_ && R > 1), "the fused expansion lives in a forward CONTIG pass of two rounds or more");
+    // CINV_: the last executed pass of a coset interpolation (ntt_coset_inverse).  The unscaled inverse rounds, then every output
+    // word is multiplied by its word of the plan's vector u[i] = shift^-bitrev(i) * N^-1 (PassArgs::cinv_u) where the scaled
+    // inverse multiplies by the constant N^-1 (phase_cinv_scale in place of phase_scale / the folded stage 0).
+    static constexpr bool CINV = CINV_;
+    static_assert(!CINV_ || (INV_ && CONTIG_), "the per-position output scaling lives in an inverse CONTIG pass");
     static constexpr int LDS_WORDS = LDS_WORDS_PADDED;
     // Register prefetch of the NEXT polynomial's tile (round 6, BASELINE config 2): the 4-byte 512-thread radix-8 kernels that run a
     // single-pass size (PassDesc::variant 1) stage their tile linearly by ordinary loads; with PREFETCH a thread requests its E words
@@ -296,6 +301,9 @@ struct PassArgs {
     const W *lde_in = nullptr;  // compact source, [batch][N >> lde_beta] words
     const W *lde_s = nullptr;   // coset vector, table form, max(N >> lde_beta, 4) words (periodic when shorter than 4)
     int lde_beta = 0;           // log2 of the blow-up, 1..4
+    // Coset interpolation (PassCfg::CINV kernels only; null for every other launch): word j of every row of the output is
+    // multiplied by cinv_u[j], table form, N words (position in the row only: cinv_word)
+    const W *cinv_u = nullptr;
 #if defined(NTT_PHASE_STAMPS)
     unsigned long long *stamps;  // [stamp_records][STAMP_RECORD] 64-bit slots, one record per wave of the launch (null: stamps go to a dummy record)
     uint32_t stamp_records;
@@ -1291,8 +1299,54 @@ NTT_HD void phase_scale(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
     for (int e = 0; e < Cfg::E; ++e) c.x[e] = a.field.mul(c.x[e], a.scale);
 }
 
+// ---- coset interpolation (Cfg::CINV; ntt_coset_inverse's last pass) ---------------------------------------------------------
+// After round 0 of a CONTIG pass thread q of the unit at `hi` holds the E consecutive words hi * 2^LOG_M + q * E + e of its
+// row (window 0: phase_init, lds_base[0]), so its words of the vector are ONE aligned run of E words that depends on the
+// position only -- not on the polynomial, not on the layout of the input.  hi < 2^(n - LOG_M) and q < 2^(LOG_M - LOG_E):
+// the run ends at or before word 2^n, the read never leaves the vector.  One rule for the device's 16-byte fetches and for
+// the host model's per-word reads.
+template <class Cfg>
+NTT_HD uint32_t cinv_word(const Ctx<Cfg> &c) {
+    return (c.hi << Cfg::LOG_M) + (c.q << Cfg::LOG_E);
+}
+
+// x[e] *= u[cinv_word + e]: the vector sweep that stands where the scaled inverse has its product by N^-1.  The words are
+// fetched 16 bytes at a time, as load_twiddles does (L2-resident: N words for the whole batch), one fetch per statement of
+// the product streams, so no more than the compiler chooses to keep in flight is ever live beside the data registers.
+// 4-byte words: m32_mul4v_* = the sweep's m32_mul4_* with four vector multipliers (same instruction count); 8-byte words:
+// the "v" forms of the two-product streams.  Any 64-bit / lazy representative in, canonical word out (tests/test_gl_asm_sim.py).
+template <class Cfg, int M32_MODE = -1>
+NTT_HD void phase_cinv_scale(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
+    using W = typename Cfg::W;
+    const W *u = a.cinv_u + cinv_word<Cfg>(c);
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int V = Cfg::E < Cfg::VW ? Cfg::E : Cfg::VW;
+    static_for<0, Cfg::E / V>([&](auto kk) {
+        constexpr int e = V * decltype(kk)::value;
+        const Chunk<W, V> ch = *reinterpret_cast<const Chunk<W, V> *>(u + e);
+        if constexpr (std::is_same<typename Cfg::F, FieldM32>::value && V == 4 && M32_MODE >= 0) {
+            if constexpr (M32_MODE == 0) m32_mul4v_lazy(c.x[e], c.x[e + 1], c.x[e + 2], c.x[e + 3], ch.v[0], ch.v[1], ch.v[2], ch.v[3], a.field.p, a.field.pinv);
+            else if constexpr (M32_MODE == 1) m32_mul4v_small(c.x[e], c.x[e + 1], c.x[e + 2], c.x[e + 3], ch.v[0], ch.v[1], ch.v[2], ch.v[3], a.field.p, a.field.pinv);
+            else m32_mul4v_any(c.x[e], c.x[e + 1], c.x[e + 2], c.x[e + 3], ch.v[0], ch.v[1], ch.v[2], ch.v[3], a.field.p, a.field.pinv);
+        } else if constexpr (std::is_same<typename Cfg::F, FieldGL>::value && V == 2) {
+            if constexpr (Cfg::LOG_E < 4) gl_mul2_v_lo(c.x[e], ch.v[0], c.x[e + 1], ch.v[1]);
+            else gl_mul2_v(c.x[e], ch.v[0], c.x[e + 1], ch.v[1]);
+        } else if constexpr (std::is_same<typename Cfg::F, FieldM64>::value && V == 2) {
+            if constexpr (Cfg::LOG_E < 4) m64_mul2_v_lo(c.x[e], ch.v[0], c.x[e + 1], ch.v[1], a.field.p, a.field.pinv);
+            else m64_mul2_v(c.x[e], ch.v[0], c.x[e + 1], ch.v[1], a.field.p, a.field.pinv);
+        } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i) c.x[e + i] = a.field.mul(c.x[e + i], ch.v[i]);
+        }
+    });
+#else
+    for (int e = 0; e < Cfg::E; ++e) c.x[e] = a.field.mul(c.x[e], u[e]);
+#endif
+}
+
 // Lazy 4-byte-word arithmetic (p < 2^30) leaves values in [0, 2p): bring them to [0, p) once, in the pass that
-// finishes the transform (the scaled inverse already ends with a canonical product).  On canonical input the
+// finishes the transform (the scaled inverse already ends with a canonical product, and so does the coset interpolation's
+// vector sweep: Cfg::CINV).  On canonical input the
 // subtraction wraps and the minimum is the input itself, so the host model may run it unconditionally.
 template <class Cfg>
 NTT_HD void phase_canon(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
@@ -1300,7 +1354,7 @@ NTT_HD void phase_canon(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
         // Goldilocks inverse (DIT) butterflies keep sums and differences as ANY 64-bit representative (their
         // other operand is always a canonical product); the scaled inverse ends with a canonical product, the
         // unscaled one is canonicalised here: x >= p  <=>  x + (2^32 - 1) carries, and the wrapped sum is x - p.
-        if (a.do_scale) return;
+        if (Cfg::CINV || a.do_scale) return;
 #pragma unroll
         for (int e = 0; e < Cfg::E; ++e) {
             const uint64_t t = c.x[e] + 0xFFFFFFFFull;
@@ -1309,7 +1363,7 @@ NTT_HD void phase_canon(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
     }
     if constexpr (std::is_same<typename Cfg::F, FieldM32>::value && Cfg::E >= 8) {
         const bool last = Cfg::INV ? Cfg::CONTIG : (a.s0 + Cfg::LOG_M == a.n);
-        if (a.field.p >= 0x40000000u || !last || (Cfg::INV && a.do_scale)) return;
+        if (a.field.p >= 0x40000000u || !last || Cfg::CINV || (Cfg::INV && a.do_scale)) return;
 #pragma unroll
         for (int e = 0; e < Cfg::E; ++e) {
             const uint32_t d = c.x[e] - a.field.p;
@@ -1419,7 +1473,10 @@ NTT_HD void run_pass(Exec &ex, const PassArgs<Cfg> &a) {
         });
         // (a configuration that CAN fold the scaling never runs the sweep: its launcher picks SC whenever do_scale is set, so
         // the unscaled kernel carries neither the sweep's code nor its 24 scratch registers)
-        if constexpr (Cfg::INV && !SC && !fold_scale<Cfg>()) ex.each([&](C &c) { phase_scale<Cfg, M32_MODE>(c, a); });
+        // (a coset interpolation runs the unscaled rounds and multiplies by its vector instead: N^-1 is inside the vector, and the
+        // shared argument fill never hands such a kernel a scaled launch, so its SC form is never the one that runs)
+        if constexpr (Cfg::CINV) ex.each([&](C &c) { phase_cinv_scale<Cfg, M32_MODE>(c, a); });
+        else if constexpr (Cfg::INV && !SC && !fold_scale<Cfg>()) ex.each([&](C &c) { phase_scale<Cfg, M32_MODE>(c, a); });
         ex.each([&](C &c) { phase_canon<Cfg>(c, a); });
         if constexpr (Cfg::DIRECT_STORE) {
             ex.each([&](C &c) { phase_store_direct<Cfg, LAST>(c, a, it); });

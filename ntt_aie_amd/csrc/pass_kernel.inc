@@ -128,6 +128,7 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
     // the fused expansion runs in its own kernels and nowhere else (never beside LDS-DMA or the register prefetch: PassCfg::LDE);
     // refused here before anything else, and again by the fill below, which the host index model shares
     if ((e.lde_beta != 0) != Cfg::LDE) return hipErrorInvalidValue;
+    if ((e.cinv_u != nullptr) != Cfg::CINV) return hipErrorInvalidValue;  // ... likewise the coset interpolation's vector (PassCfg::CINV)
     PassGeom g = pass_geometry_of<Cfg>(e);
 #if defined(NTT_EXPERIMENT)
     if ((e.dbg & 0x1000) && g.grid_x == 1 && g.ppw == 1) {
@@ -161,7 +162,7 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
         }
         return hipSuccess;
     }
-    if constexpr (fold_scale<Cfg>()) {
+    if constexpr (fold_scale<Cfg>() && !Cfg::CINV) {  // (a coset interpolation is never a scaled launch: fill_pass_args)
         if (a.tw_sc != nullptr) {  // scaled inverse: N^-1 rides on stage 0 (no scaling sweep)
             hipLaunchKernelGGL((pass_kernel<Cfg, true>), dim3(g.grid_x, g.grid_y, 1), dim3(Cfg::NT, 1, 1), 0, s, a);
             return hipGetLastError();

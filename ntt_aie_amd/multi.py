@@ -57,6 +57,12 @@ class MultiDevicePlan:
         if self._cloned:
             self._clone_all()
 
+    def set_coset_inverse(self, shift: int) -> None:
+        """NTTPlan.set_coset_inverse on the first plan; the clones carry the setting and the vector (ntt_plan_clone)."""
+        self.plans[0].set_coset_inverse(shift)
+        if self._cloned:
+            self._clone_all()
+
     # ---- shards -------------------------------------------------------------------------------------------------------
     def rows(self, batch: int) -> list[tuple[int, int]]:
         """Row range [lo, hi) of the [batch][N] job held by each device (contiguous, sizes differ by at most one)."""
@@ -115,6 +121,10 @@ class MultiDevicePlan:
         # (a device whose shard is empty gets an empty [0][N] result, not its input back)
         outs = [y if (y is not None or x.shape[0]) else empty_out(pl, x, st) for pl, st, x, y in zip(self.plans, self.streams, shards, outs)]
         return self._each(lambda pl, x, y, st: pl.lde(x, y, layout=layout, stream=st), shards, outs)
+
+    def coset_inverse(self, shards: list[torch.Tensor], outs: list[torch.Tensor] | None = None, layout: int = LAYOUT_NATURAL):
+        """NTTPlan.coset_inverse by rows, one launch sequence per device."""
+        return self._each(lambda pl, x, y, st: pl.coset_inverse(x, y, layout=layout, stream=st), shards, outs)
 
     def close(self) -> None:
         for pl in self.plans:

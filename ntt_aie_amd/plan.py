@@ -162,6 +162,21 @@ class NTTPlan:
         """Does lde() expand inside the first pass (True from logn = 5 on) or through the separate expansion kernel."""
         return bool(_lib.lib().ntt_plan_info(self._h, 10))
 
+    # ---- coset interpolation: values on shift * <w_M> back to coefficients ------------
+    def set_coset_inverse(self, shift: int) -> None:
+        """Configure coset_inverse() (ntt_plan_set_coset_inverse): the plan builds its M-word vector shift^-bitrev(i) * M^-1 on the
+        device.  Independent of set_coset().  Configuration: call before the plan is shared between threads."""
+        check(_lib.lib().ntt_plan_set_coset_inverse(self._h, shift), "ntt_plan_set_coset_inverse")
+
+    @property
+    def coset_inverse_set(self) -> bool:
+        return bool(_lib.lib().ntt_plan_info(self._h, 11))
+
+    @property
+    def coset_inverse_fused(self) -> bool:
+        """Does coset_inverse() scale inside the inverse's last pass (True from logn = 5 on) or through the separate row-scaling kernel."""
+        return bool(_lib.lib().ntt_plan_info(self._h, 12))
+
     @property
     def has_inverse(self) -> bool:
         return bool(_lib.lib().ntt_plan_info(self._h, 4))
@@ -249,6 +264,15 @@ class NTTPlan:
         b = self._batch(inp, out)
         check(_lib.lib().ntt_inverse(self._h, inp.data_ptr(), out.data_ptr(), b, layout, int(scale),
                                      self._stream(stream)), "ntt_inverse")
+        return out
+
+    def coset_inverse(self, inp: torch.Tensor, out: torch.Tensor | None = None, layout: int = LAYOUT_NATURAL, stream=None) -> torch.Tensor:
+        """Coset interpolation (ntt_coset_inverse): the scaled inverse of every row of `inp` (given in `layout`), word i times
+        shift^-bitrev(i).  With kind-1 tables and values on shift * <w_M> in, the coefficients come out in the bit-reversed order
+        lde() consumes.  `out` may be `inp`."""
+        out = self._out_like(inp, stream) if out is None else out
+        b = self._batch(inp, out)
+        check(_lib.lib().ntt_coset_inverse(self._h, inp.data_ptr(), out.data_ptr(), b, layout, self._stream(stream)), "ntt_coset_inverse")
         return out
 
     def pointwise_mul(self, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None,

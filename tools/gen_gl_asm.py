@@ -415,14 +415,15 @@ def stream(kind, nb=2, vbase=104, mode=None):
         return schedule([butterfly64(kind, b, vbase) for b in range(nb)])
     return schedule([butterfly(kind, b, vbase) for b in range(nb)])
 
-def emit32(kind, nb, mode, vbase=M32_VBASE):
+def emit32(kind, nb, mode, vbase=M32_VBASE, vec_t=False):
+    """vec_t (mul32 only): one multiplier per word in VGPRs instead of the one wave-uniform constant -- the same stream."""
     lists = [butterfly32(kind, b, mode, vbase) for b in range(nb)]
     lines = schedule(lists)
     nops = sum(1 for l in lines if l.startswith("s_nop"))
-    name = f"m32_{kind[:3]}{nb}_{mode}"
+    name = f"m32_{kind[:3]}{nb}{'v' if vec_t else ''}_{mode}"
     what = {"lazy": "p < 2^30, values in [0, 2p)", "small": "p < 2^31", "any": "any odd p < 2^32"}[mode]
     if kind == "mul32":
-        args = ", ".join(f"uint32_t &x{b}" for b in range(nb)) + ", uint32_t t"
+        args = ", ".join(f"uint32_t &x{b}" for b in range(nb)) + ", " + (", ".join(f"uint32_t t{b}" for b in range(nb)) if vec_t else "uint32_t t")
     else:
         args = ", ".join(f"uint32_t &x{b}, uint32_t &y{b}, uint32_t t{b}" for b in range(nb))
     extra = ", uint32_t p2" if mode == "lazy" and kind != "mul32" else ""
@@ -437,7 +438,7 @@ def emit32(kind, nb, mode, vbase=M32_VBASE):
     for b in range(nb):
         if kind == "mul32":
             outs += [f'[x_{b}] "+v"(x{b})'] + [f'[{r}{b}] "=&v"({r}{b})' for r in ("a_", "b_")]
-            ins_ += [f'[t_{b}] "s"(t)']  # the one wave-uniform multiplier
+            ins_ += [f'[t_{b}] "v"(t{b})' if vec_t else f'[t_{b}] "s"(t)']  # per-word multipliers, or the one wave-uniform multiplier
         else:
             outs += [f'[x_{b}] "+v"(x{b})', f'[y_{b}] "+v"(y{b})']
             outs += [f'[{r}{b}] "=&v"({r}{b})' for r in ("a_", "b_", "c_")]
@@ -665,6 +666,10 @@ def main():
             out.append(txt)
             out.append("")
             print(f"{kind} x4 {mode}: {n} instructions, {nops} nops", file=sys.stderr)
+            if kind == "mul32":  # the coset interpolation's vector sweep (pass.h: phase_cinv_scale): a multiplier per word
+                txt, n, nops = emit32(kind, 4, mode, vec_t=True)
+                out.append(txt)
+                out.append("")
     # general odd 64-bit modulus: heavy kernels (radix-16: scratch v[104:127], p in v[102:103]) and light ones (radix-8: v[72:95], v[96:97])
     for kind in ("fwd64", "inv64", "mul64"):
         for tw in ("v", "s"):
