@@ -128,7 +128,9 @@ int ntt_plan_get_twiddles(ntt_plan_t plan, int inverse, void *host_T);
  * 9 the coset blow-up log2 set by ntt_plan_set_coset (0 = not set), 10 whether ntt_lde on this plan expands inside its first
  * pass (1) or runs the separate expansion kernel first (0; also 0 while no coset is set);
  * 11 whether a coset-inverse shift is set (ntt_plan_set_coset_inverse), 12 whether ntt_coset_inverse on this plan scales inside
- * its last pass (1) or runs the separate row-scaling kernel after the transform (0; also 0 while nothing is set) */
+ * its last pass (1) or runs the separate row-scaling kernel after the transform (0; also 0 while nothing is set);
+ * 13 number of passes of the columns decomposition (ntt_forward_columns / ntt_inverse_columns; 0 when logn < 4),
+ * 96 + i: stages in pass i of it, 128 + i: first stage of pass i of it (every pass is a column pass) */
 int64_t ntt_plan_info(ntt_plan_t plan, int what);
 
 /* The stage decomposition into HBM passes is chosen at LAUNCH, by batch size, among alternatives fixed at plan creation
@@ -213,6 +215,45 @@ int ntt_lde(ntt_plan_t plan, const void *d_in, void *d_out, size_t batch, int ou
  * NTT_E_NOTABLE / NTT_E_NOTINVERTIBLE / NTT_E_LAYOUT as ntt_inverse.  batch == 0 is NTT_OK. */
 int ntt_plan_set_coset_inverse(ntt_plan_t plan, uint64_t shift);
 int ntt_coset_inverse(ntt_plan_t plan, const void *d_in, void *d_out, size_t batch, int in_layout, void *stream);
+
+/* ---- row-major matrix batches: transform the COLUMNS of [N][pitch] (no reference counterpart) ----
+ * A Plonky3-style trace is a row-major matrix [N][width]: each column is a polynomial, each row is what gets hashed into a
+ * Merkle leaf.  These two entry points transform every column where it lies -- no transpose before or after.
+ *
+ * Layout.  `count` matrices lie one after another; word (m, r, c) is at ((m * N + r) * pitch + c), r < N = 2^logn of the plan,
+ * c < width <= pitch.  Column c of matrix m is one polynomial.  Defined at network level, like everything above: the result equals
+ * exactly what ntt_forward / ntt_inverse(scale) with NTT_LAYOUT_NATURAL give on that column laid out contiguously -- for any table,
+ * all three word classes, `scale` as in ntt_inverse.
+ * Footprint.  Only words with c < width are ever read or written.  Padding columns [width, pitch) of d_in may hold anything,
+ * non-canonical words included; padding columns of d_out keep their contents.  A buffer of exactly
+ * (count * N - 1) * pitch + width words is sufficient (the last row needs no padding).
+ * In place and overlap.  d_in == d_out is allowed; any other overlap of the two byte ranges is NTT_E_ARG, as in ntt_lde.  Out of
+ * place, the first executed pass reads d_in and writes d_out, the remaining passes run in place on d_out.
+ * Launch.  Asynchronous on `stream`; no allocation, no host synchronisation.  count == 0 or width == 0 is NTT_OK.
+ * Alignment.  Pointers 16-byte aligned, as everywhere.  pitch is any value >= width: the passes move single words, an odd pitch
+ * is legal.  A pitch that is a multiple of 128 bytes is recommended: a workgroup's tile is 128 bytes of consecutive columns per
+ * row (16 columns of 8-byte words, 32 of 4-byte words), which is then exactly one cache line per row instead of parts of two.
+ * A tile whose columns lie partly or wholly at or beyond `width` idles those lanes: a width below 16 / 32 columns wastes the
+ * rest of the tile and is still correct.
+ *
+ * How.  Pad every row to 2^w words in thought: the matrix is then, bit for bit, ONE polynomial of 2^(logn + w) words whose word
+ * r * 2^w + c is (r, c).  Stage w + s of the size-2^(logn + w) network pairs words 2^(w + s) apart -- rows 2^s apart, same column
+ * -- and wants the twiddle of block (index >> (w + s + 1)) = (r >> (s + 1)) among 2^(logn - s - 1) blocks: T[2^(logn-s-1) + block],
+ * the plan's own N-word table at the index stage s of a single column uses.  So stages w .. w + logn - 1 of the virtual network
+ * ARE the per-column networks, all 2^w columns at once, with twiddles that do not depend on the column.  The stages run as the
+ * library's column passes (4..8 stages each, the fewest passes, split evenly: ntt_plan_info 13 / 96+ / 128+) launched on
+ * (logn + w, first stage + w); only the word -> address map differs (row * pitch + column), and lanes at columns >= width are
+ * idle.  w = max(LOG_C, ceil_log2(width)), LOG_C = 4 for 8-byte words and 5 for 4-byte words.  No contiguous pass, no transpose.
+ *
+ * Errors (existing codes only).  NTT_E_ARG: null or misaligned pointer, width > pitch, partial overlap, count >= 2^31, or a matrix
+ * too large for the 32-bit in-tile byte offsets: the rule is N * pitch <= 2^NTT_MAX_LOGN words and logn + w <= NTT_MAX_LOGN, so
+ * every index rule a size-2^28 transform obeys covers this one too.  NTT_E_LOGN: a plan with logn < 4 -- no column kernel
+ * shape exists below four stages, and a prover has no such trace.  NTT_E_NOTABLE / NTT_E_NOTINVERTIBLE as for ntt_forward /
+ * ntt_inverse.
+ * Not provided: other layouts (both entry points are natural order only), a coset shift on columns, multi-device plans. */
+int ntt_forward_columns(ntt_plan_t plan, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, void *stream);
+int ntt_inverse_columns(ntt_plan_t plan, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, int scale,
+                        void *stream);
 
 /* Profiling twin of ntt_forward (the reference brackets one kernel iteration with
  * trace events, src/aie_core.cc:129-131, src/aie2.py:168,316): identical launches

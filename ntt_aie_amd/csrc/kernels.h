@@ -21,6 +21,17 @@ NTT_PASS_UNIT(FieldGL) NTT_PASS_UNIT(FieldM32) NTT_PASS_UNIT(FieldM64)
 #undef NTT_PASS_UNIT
 hipError_t launch_pass(bool inverse, bool contig, int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field
 
+// The matrix twins of the column passes (launch.h: mat_dispatch), same units, same instantiation rule.  a.n / a.s0 are the virtual
+// polynomial's, a.mat_* the matrix geometry; hipErrorInvalidValue outside 4..8 stages or when fill_pass_args refuses the arguments.
+template <class F, bool INV>
+hipError_t launch_mat_of(int log_m, const ErasedArgs &a, hipStream_t s);
+#define NTT_MAT_UNIT(F) \
+    extern template hipError_t launch_mat_of<F, false>(int, const ErasedArgs &, hipStream_t); \
+    extern template hipError_t launch_mat_of<F, true>(int, const ErasedArgs &, hipStream_t);
+NTT_MAT_UNIT(FieldGL) NTT_MAT_UNIT(FieldM32) NTT_MAT_UNIT(FieldM64)
+#undef NTT_MAT_UNIT
+hipError_t launch_mat_pass(bool inverse, int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field
+
 // Fused middle of a negacyclic product (pass.h: run_product_pass): per 2^log_m-word unit, inverse CONTIG pass of a.in
 // and of a.in2, word-by-word product * pw_scale, forward CONTIG pass -> a.out.  tw = inverse table, tw2 = forward table.
 // hipErrorInvalidValue when this (word size, log_m) has no fused kernel or the batch does not fit one grid (launch.h:

@@ -61,6 +61,9 @@ struct ErasedArgs {
     const void *lde_s;    // lde_beta == 0: an ordinary launch
     int lde_beta;
     const void *cinv_u;   // inverse CONTIG pass of ntt_coset_inverse: the per-position output vector (PassArgs::cinv_u); null: an ordinary launch
+    int mat_w;            // column pass over row-major matrices (ntt_*_columns; PassArgs::mat_*): log2 virtual row length / row pitch /
+    uint32_t mat_pitch;   // live columns.  n and s0 are then the virtual polynomial's, batch counts matrices.  All zero: an ordinary
+    uint32_t mat_width;   // launch
 #if defined(NTT_PHASE_STAMPS)
     void *stamps;            // diagnostic build: PassArgs::stamps / stamp_records (ntt_stamps_set)
     uint32_t stamp_records;
@@ -150,9 +153,32 @@ bool pass_dispatch(bool contig, int log_m, const ErasedArgs &a, Fn &&fn) {
     return contig_dispatch<F, INV, false>(log_m, a, last_pass, fn);
 }
 
+// The matrix twin of the column pass of log_m stages (PassCfg::MAT, pass.h: ColMatCfg); the only kernels a launch with the matrix
+// arguments may run, and no other launch may run them (fill_pass_args).
+template <class F, bool INV, class Fn>
+bool mat_dispatch(int log_m, Fn &&fn) {
+    return with_log_m<host::MIN_COL_LOG_M, host::MAX_COL_LOG_M>(log_m, [&](auto m) { fn(CfgTag<ColMatCfg<F, decltype(m)::value, INV>>{}); });
+}
+
+// Largest matrix (N * pitch words) and virtual polynomial a matrix launch takes: those of a size-2^28 transform, so that every
+// 32-bit lane / element byte offset a column pass forms stays where it is for the largest ordinary plan (NTT_MAX_LOGN)
+constexpr int MAT_MAX_LOG_WORDS = 28;
+inline uint64_t mat_words(const ErasedArgs &e) { return e.n >= e.mat_w && e.n - e.mat_w < 32 ? ((uint64_t) 1 << (e.n - e.mat_w)) * e.mat_pitch : ~(uint64_t) 0; }
+// Unit slots of a MAT workgroup that are used.  A small matrix leaves room for several per workgroup (log_up > 0), whose lane
+// offsets reach 2^log_up * N * pitch words whatever the width: no more matrices share a workgroup than keep that within
+// 2^MAT_MAX_LOG_WORDS; lanes of the slots beyond are dead (pass.h: Ctx::live).
+inline int mat_log_u(const ErasedArgs &e, int log_m, int log_c, int log_u) {
+    const int one_matrix = (e.s0 - log_c) + (e.n - e.s0 - log_m);  // log2 units of one matrix
+    int k = 0;
+    while (one_matrix + k < log_u && (mat_words(e) << (k + 1)) <= ((uint64_t) 1 << MAT_MAX_LOG_WORDS)) ++k;
+    return one_matrix + k < log_u ? one_matrix + k : log_u;
+}
+
 template <class Cfg>
 PassGeom pass_geometry_of(const ErasedArgs &e) {
-    return pass_geometry(e.n, e.s0, Cfg::LOG_M, Cfg::LOG_C, Cfg::LOG_U, Cfg::CONTIG, e.batch, e.target_wgs, Cfg::PPW_CAP);
+    int log_u = Cfg::LOG_U;
+    if constexpr (Cfg::MAT) log_u = mat_log_u(e, Cfg::LOG_M, Cfg::LOG_C, Cfg::LOG_U);
+    return pass_geometry(e.n, e.s0, Cfg::LOG_M, Cfg::LOG_C, log_u, Cfg::CONTIG, e.batch, e.target_wgs, Cfg::PPW_CAP);
 }
 
 // The kernel's argument block for this launch and geometry; false = the launch is refused.  a.tw_sc is set exactly when
@@ -195,6 +221,18 @@ bool fill_pass_args(const ErasedArgs &e, const PassGeom &g, PassArgs<Cfg> &a) {
     if constexpr (Cfg::CINV) {
         if (e.s0 != 0 || e.do_scale || e.tw_sc || e.in2) return false;
         a.cinv_u = (const W *) e.cinv_u;
+    }
+    // ... and the matrix addressing (PassCfg::MAT): its three arguments are refused on any other configuration, a twin is refused
+    // without them or with anything a column pass over matrices does not do
+    if ((e.mat_w != 0 || e.mat_pitch != 0 || e.mat_width != 0) != Cfg::MAT) return false;
+    if constexpr (Cfg::MAT) {
+        if (e.mat_w < Cfg::LOG_C || e.mat_w > e.s0 || e.s0 + Cfg::LOG_M > e.n || e.n > MAT_MAX_LOG_WORDS) return false;
+        if (e.mat_width == 0 || e.mat_width > e.mat_pitch || e.mat_width > (1u << e.mat_w)) return false;
+        if (mat_words(e) > ((uint64_t) 1 << MAT_MAX_LOG_WORDS)) return false;
+        if (e.layout != LAYOUT_NATURAL || e.in2 || e.tw_sc || (e.do_scale && !(Cfg::INV && e.s0 == e.mat_w))) return false;
+        a.mat_w = e.mat_w;
+        a.mat_pitch = e.mat_pitch;
+        a.mat_width = e.mat_width;
     }
     if constexpr (fold_scale<Cfg>()) {
         if (e.do_scale && e.tw_sc == nullptr) return false;  // these kernels have no scaling sweep

@@ -241,6 +241,13 @@ hipError_t launch_pass(bool inverse, bool contig, int log_m, const ErasedArgs &a
     });
 }
 
+hipError_t launch_mat_pass(bool inverse, int log_m, const ErasedArgs &a, hipStream_t s) {
+    return with_field(a.field, [&](auto f) {
+        using F = decltype(f);
+        return inverse ? launch_mat_of<F, true>(log_m, a, s) : launch_mat_of<F, false>(log_m, a, s);
+    });
+}
+
 hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s) {
     return with_field(a.field, [&](auto f) { return launch_product_mid_of<decltype(f)>(log_m, a, s); });
 }

@@ -103,6 +103,7 @@ struct ntt_plan {
     std::mutex counter_mu;                    // ... which is the only entry point that writes plan-owned state after creation
     std::vector<PassDesc> passes;  // = alts[0].passes: the default decomposition (ntt_plan_info 3 / 32+ / 64+)
     std::vector<PlanAlt> alts;     // launch-time alternatives, ascending min_batch (plan.h: plan_alternatives)
+    std::vector<PassDesc> col_passes;  // ntt_forward_columns / ntt_inverse_columns: every stage as a column pass (plan.h: plan_column_passes)
     int forced_alt = -1;           // ntt_plan_set_policy: -1 = by batch, k >= 0 = always alternative k
     // ntt_plan_set_coset: low-degree extension onto shift * <w_N> from N >> lde_beta coefficients (0 = not set)
     int lde_beta = 0;
@@ -309,6 +310,55 @@ int run_inverse(ntt_plan *pl, const void *d_in, void *d_out, size_t batch, int l
     });
 }
 
+// ntt_forward_columns / ntt_inverse_columns: count matrices [N][pitch], the first `width` words of a row are live.  Every stage is a
+// column pass over the virtual polynomial of 2^(logn + w) words (pass.h: PassCfg::MAT), w = max(LOG_C, ceil_log2(width)).
+int run_columns(ntt_plan *pl, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, bool inverse, int scale, void *stream) {
+    if (!pl) return NTT_E_ARG;
+    if (pl->logn < MIN_COL_LOG_M) return NTT_E_LOGN;  // no column kernel shape below four stages
+    if (width > pitch) return NTT_E_ARG;
+    const bool empty = count == 0 || width == 0;
+    if (!empty) {
+        if (!d_in || !d_out) return NTT_E_ARG;
+        if (((uintptr_t) d_in | (uintptr_t) d_out) & 15u) return NTT_E_ARG;
+    }
+    if (!pl->has_table) return NTT_E_NOTABLE;
+    if (inverse && !pl->has_inv) return NTT_E_NOTINVERTIBLE;
+    if (empty) return NTT_OK;
+    // size rule: N * pitch <= 2^NTT_MAX_LOGN words and logn + w <= NTT_MAX_LOGN -- what a size-2^28 transform obeys
+    int w = ntt::col_log_c(pl->word_bytes);
+    while (((size_t) 1 << w) < width && w < NTT_MAX_LOGN) ++w;
+    if (pl->logn + w > NTT_MAX_LOGN || pitch > ((size_t) 1 << (NTT_MAX_LOGN - pl->logn)) || count > 0x7FFFFFFFull) return NTT_E_ARG;
+    const size_t N = (size_t) 1 << pl->logn;
+    if (count > (SIZE_MAX / 16) / (N * pitch)) return NTT_E_ARG;
+    const size_t foot = ((count * N - 1) * pitch + width) * (size_t) pl->word_bytes;  // bytes from the first to the last live word
+    const uintptr_t in0 = (uintptr_t) d_in, out0 = (uintptr_t) d_out;
+    if (in0 != out0 && in0 < out0 + foot && out0 < in0 + foot) return NTT_E_ARG;  // in place, or apart
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    hipStream_t s = (hipStream_t) stream;
+    RoctxRange whole(inverse ? "ntt_inverse_columns" : "ntt_forward_columns");
+    const std::vector<PassDesc> &passes = pl->col_passes;
+    const void *src = d_in;
+    for (size_t k = 0; k < passes.size(); k++) {
+        const PassDesc &pd = passes[inverse ? passes.size() - 1 - k : k];
+        RoctxRange pass(inverse ? "inv columns pass" : "fwd columns pass", 0, pd.s0, pd.log_m);
+        ntt::ErasedArgs a = base_args(pl, pd, src, d_out, count);
+        a.n = pl->logn + w;
+        a.s0 = pd.s0 + w;
+        a.mat_w = w;
+        a.mat_pitch = (uint32_t) pitch;
+        a.mat_width = (uint32_t) width;
+        a.tw = inverse ? pl->d_tw_inv : pl->d_tw_fwd;
+        a.layout = NTT_LAYOUT_NATURAL;
+        a.do_scale = (inverse && scale && pd.s0 == 0) ? 1 : 0;  // the sweep of the last executed pass, the one that holds stage 0
+        a.scale = pl->scale_tf;
+        const hipError_t e = ntt::launch_mat_pass(inverse, pd.log_m, a, s);
+        if (e != hipSuccess) return (int) e;
+        src = d_out;
+    }
+    return NTT_OK;
+}
+
 // device-to-device, no host copy: over xGMI when the devices differ (hipMemcpyPeer), which is what the
 // reference's on-chip table broadcast does below its host (src/aie2.py:96-104)
 hipError_t copy_d2d(void *dst, int dst_dev, const void *from, int from_dev, size_t bytes) {
@@ -320,7 +370,7 @@ hipError_t copy_d2d(void *dst, int dst_dev, const void *from, int from_dev, size
 
 extern "C" {
 
-int ntt_version(void) { return 400; /* 0.4.0 */ }
+int ntt_version(void) { return 500; /* 0.5.0 */ }
 
 #if defined(NTT_PHASE_STAMPS)
 // Diagnostic side build only (tools/ab_build.sh stamps -DNTT_PHASE_STAMPS -> ab/libntt_stamps.so; tools/phase_stamps.py): where
@@ -390,6 +440,7 @@ int ntt_plan_create(ntt_plan_t *out, int logn, uint64_t p, int word_bytes, int d
     pl->scale_tf = to_table_form(pl->ninv_plain, p, word_bytes);
     pl->alts = plan_alternatives(logn, word_bytes, p);
     pl->passes = pl->alts[0].passes;
+    pl->col_passes = plan_column_passes(logn);
 #if defined(NTT_EXPERIMENT)
     // Experiment knobs exist only in libntt_hip_exp.so (make exp; tools/): the product library reads NO environment
     // variable, so a stray NTT_DEBUG_FLAGS in a user's shell cannot redirect loads and stores.
@@ -567,6 +618,7 @@ int64_t ntt_plan_info(ntt_plan_t pl, int what) NTT_GUARD {
         case 10: return lde_fused(pl) ? 1 : 0;
         case 11: return pl->cinv_set ? 1 : 0;
         case 12: return cinv_fused(pl) ? 1 : 0;
+        case 13: return (int64_t) pl->col_passes.size();
         case 8: {  // capacity for ntt_forward_profile whatever the batch
             size_t k = 0;
             for (const PlanAlt &a : pl->alts) k = a.passes.size() > k ? a.passes.size() : k;
@@ -587,6 +639,8 @@ int64_t ntt_plan_info(ntt_plan_t pl, int what) NTT_GUARD {
         const int k = (what - 512) % 16;
         return k < (int) alt.passes.size() ? alt.passes[(size_t) k].variant : NTT_E_ARG;
     }
+    if (what >= 96 && what < 96 + (int) pl->col_passes.size()) return pl->col_passes[what - 96].log_m;
+    if (what >= 128 && what < 128 + (int) pl->col_passes.size()) return pl->col_passes[what - 128].s0;
     if (what >= 32 && what < 32 + (int) pl->passes.size()) return pl->passes[what - 32].log_m;
     if (what >= 64 && what < 64 + (int) pl->passes.size()) return pl->passes[what - 64].s0;
 #if defined(NTT_EXPERIMENT)
@@ -673,6 +727,7 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
     if (rc != NTT_OK) return rc;
     pl->alts = src->alts;  // an experiment split or a forced policy travels with the plan
     pl->passes = src->passes;
+    pl->col_passes = src->col_passes;
     pl->forced_alt = src->forced_alt;
     pl->target_wgs = src->target_wgs;
     pl->target_wgs_col = src->target_wgs_col;
@@ -815,6 +870,14 @@ int ntt_inverse(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int 
     DeviceGuard g(pl->device);
     if (g.err != hipSuccess) return (int) g.err;
     return run_inverse(pl, d_in, d_out, batch, in_layout, scale, (hipStream_t) stream);
+} NTT_GUARD_END
+
+int ntt_forward_columns(ntt_plan_t pl, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, void *stream) NTT_GUARD {
+    return run_columns(pl, d_in, d_out, width, pitch, count, false, 0, stream);
+} NTT_GUARD_END
+
+int ntt_inverse_columns(ntt_plan_t pl, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, int scale, void *stream) NTT_GUARD {
+    return run_columns(pl, d_in, d_out, width, pitch, count, true, scale, stream);
 } NTT_GUARD_END
 
 int ntt_coset_inverse(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int in_layout, void *stream) NTT_GUARD {

@@ -117,7 +117,7 @@ NTT_HD void static_for(Fn &&f) {
 }
 
 template <class F_, int LOG_M_, int LOG_C_, bool CONTIG_, bool INV_, int PRELOAD_MASK_ = 0xF, int LOG_E_ = 4,
-          int LOG_NT_ = LOG_NT, bool ALLOW_DMA_ = true, bool LDE_ = false, bool CINV_ = false>
+          int LOG_NT_ = LOG_NT, bool ALLOW_DMA_ = true, bool LDE_ = false, bool CINV_ = false, bool MAT_ = false>
 struct PassCfg {
     using F = F_;
     using W = typename F::W;
@@ -197,6 +197,13 @@ struct PassCfg {
     // inverse multiplies by the constant N^-1 (phase_cinv_scale in place of phase_scale / the folded stage 0).
     static constexpr bool CINV = CINV_;
     static_assert(!CINV_ || (INV_ && CONTIG_), "the per-position output scaling lives in an inverse CONTIG pass");
+    // MAT_: a column pass over row-major matrices [N][pitch] (ntt_forward_columns / ntt_inverse_columns): every COLUMN of a matrix is
+    // a polynomial.  A matrix whose rows are padded to 2^w words is, word for word, ONE polynomial of 2^(logN + w) words of which
+    // only stages w .. w + logN - 1 run, so the pass keeps the index model of the column pass on the virtual (n, s0) =
+    // (logN + w, s0 + w) -- the twiddle addresses never see the low w bits -- and only its word -> address map changes: word
+    // idx of the virtual view lives at (idx >> w) * pitch + (idx & (2^w - 1)) (mat_word), lanes whose column is >= width are dead.
+    static constexpr bool MAT = MAT_;
+    static_assert(!MAT_ || (!CONTIG_ && !LDE_ && !CINV_ && LOG_E_ == 4), "the matrix addressing lives in a (non-CONTIG) radix-16 column pass");
     static constexpr int LDS_WORDS = LDS_WORDS_PADDED;
     // Register prefetch of the NEXT polynomial's tile (round 6, BASELINE config 2): the 4-byte 512-thread radix-8 kernels that run a
     // single-pass size (PassDesc::variant 1) stage their tile linearly by ordinary loads; with PREFETCH a thread requests its E words
@@ -259,6 +266,10 @@ constexpr int contig_preload_mask(int log_m, int word_bytes, int log_e = 4) {
 template <class F, int LOG_M, bool INV>
 using ColPassCfg = PassCfg<F, LOG_M, col_log_c(sizeof(typename F::W)), false, INV, 0xF, 4, col_log_nt(sizeof(typename F::W)) + (LOG_M > 8 ? LOG_M - 8 : 0)>;
 
+// ... and its matrix twin (PassCfg::MAT): the same tile, rounds and workgroup, 4 .. 8 stages
+template <class F, int LOG_M, bool INV>
+using ColMatCfg = PassCfg<F, LOG_M, col_log_c(sizeof(typename F::W)), false, INV, 0xF, 4, col_log_nt(sizeof(typename F::W)), true, false, false, true>;
+
 // How the rows of blockIdx.y share the polynomial groups of the batch.  Rows [0, rows[0]) stream `ppw` groups each through
 // their resident twiddles; the next rows[1] rows ppw/2 each, then ppw/4, then ppw/8 (0 rows = level absent).  Rows are
 // dispatched in ascending order, so the launch ends with short workgroups: the drain of a launch -- slots idling while the
@@ -304,6 +315,11 @@ struct PassArgs {
     // Coset interpolation (PassCfg::CINV kernels only; null for every other launch): word j of every row of the output is
     // multiplied by cinv_u[j], table form, N words (position in the row only: cinv_word)
     const W *cinv_u = nullptr;
+    // Row-major matrices (PassCfg::MAT kernels only; all three zero = off for every other launch).  n and s0 above are those of the
+    // virtual polynomial (logN + mat_w, first stage + mat_w), `batch` counts matrices
+    int mat_w = 0;           // log2 of the virtual row length: max(LOG_C, ceil_log2(mat_width))
+    uint32_t mat_pitch = 0;  // words between two rows of a matrix
+    uint32_t mat_width = 0;  // columns that exist; a lane whose column is >= mat_width neither loads nor stores
 #if defined(NTT_PHASE_STAMPS)
     unsigned long long *stamps;  // [stamp_records][STAMP_RECORD] 64-bit slots, one record per wave of the launch (null: stamps go to a dummy record)
     uint32_t stamp_records;
@@ -325,6 +341,7 @@ struct Ctx {
     uint32_t lane_ld, lane_st;       // lane part of the global word index (first / last round)
     uint32_t lds_base[Cfg::R];       // padded LDS index of element 0 of each round
     bool active;
+    bool live;  // PassCfg::MAT: this lane's column and matrix slot exist at all (loop-invariant part of `active`)
 };
 
 // ---- index helpers -----------------------------------------------------------
@@ -351,6 +368,13 @@ NTT_HD uint32_t lane_word(const PassArgs<Cfg> &a, int b0, uint32_t q, uint32_t c
            (q_lo << a.s0) + (u_l << Cfg::LOG_C) + c;
 }
 
+// PassCfg::MAT: where word idx of the virtual view lives.  Additive over terms that occupy disjoint bit fields (no carries), so the
+// wave-uniform terms, the lane term and the element offset are mapped one by one and summed as before.
+template <class Cfg>
+NTT_HD uint32_t mat_word(const PassArgs<Cfg> &a, uint32_t idx) {
+    return (idx >> a.mat_w) * a.mat_pitch + (idx & ((1u << a.mat_w) - 1u));
+}
+
 // uniform part of the word index: workgroup tile origin + polynomial group of iteration `it`
 template <class Cfg>
 NTT_HD size_t uniform_word(const Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it, int dbg_bit = 1) {
@@ -364,6 +388,12 @@ NTT_HD size_t uniform_word(const Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it, in
     (void) dbg_bit;
     const size_t pg = (size_t) c.pg_base + (size_t) it * (uint32_t) a.pg_stride;
 #endif
+    if constexpr (Cfg::MAT) {
+        // the hi block and the matrix group are whole rows (s0 >= mat_w): scaled by the pitch in scalar registers; the lo-tile block
+        // may straddle the row / column boundary.  The polynomial-group term is the matrix stride N * pitch.
+        return (((size_t) hb << (a.log_uh + a.s0 + Cfg::LOG_M - a.mat_w)) + (pg << (a.log_up + a.n - a.mat_w))) * a.mat_pitch +
+               mat_word<Cfg>(a, ltb << (a.log_ul + Cfg::LOG_C));
+    }
     return ((size_t) hb << (a.log_uh + a.s0 + Cfg::LOG_M)) + ((size_t) ltb << (a.log_ul + Cfg::LOG_C)) +
            (pg << (a.log_up + a.n));
 }
@@ -505,6 +535,17 @@ NTT_HD void phase_init(Ctx<Cfg> &c, const PassArgs<Cfg> &a, uint32_t tid, uint32
     constexpr int LAST = Cfg::INV ? 0 : Cfg::R - 1;
     c.lane_ld = lane_word<Cfg>(a, Cfg::win(FIRST), c.q, col, u_l, u_h, c.up);
     c.lane_st = lane_word<Cfg>(a, Cfg::win(LAST), c.q, col, u_l, u_h, c.up);
+    c.live = true;
+    if constexpr (Cfg::MAT) {
+        // the lane term is mapped once, here; the batch loop carries the same two address registers as the plain column pass.
+        // Column of this lane: the low mat_w bits of (lo-tile block | lo-tile unit | tile column).  A workgroup may hold fewer
+        // matrices than it has unit slots (launch.h: mat_log_u keeps the lane offsets in 32 bits): the slots beyond are dead too.
+        const uint32_t ltb = bx & ((1u << log_ltb) - 1u);
+        const uint32_t mcol = ((ltb << (a.log_ul + Cfg::LOG_C)) + (u_l << Cfg::LOG_C) + col) & ((1u << a.mat_w) - 1u);
+        c.live = mcol < a.mat_width && (u >> (a.log_ul + a.log_uh + a.log_up)) == 0u;
+        c.lane_ld = mat_word<Cfg>(a, c.lane_ld);
+        c.lane_st = mat_word<Cfg>(a, c.lane_st);
+    }
     static_for<0, Cfg::R>([&](auto rr) {
         constexpr int r = decltype(rr)::value;
         constexpr int b0 = Cfg::win(r);
@@ -522,6 +563,7 @@ NTT_HD void phase_begin_iter(Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it) {
     // inactive when several polynomials share one workgroup (log_up > 0: ragged tail)
     const uint32_t poly = ((c.pg_base + (uint32_t) it * (uint32_t) a.pg_stride) << a.log_up) | c.up;
     c.active = Cfg::LOG_U == 0 ? true : poly < a.batch;
+    if constexpr (Cfg::MAT) c.active = c.active && c.live;
 }
 
 // Word offset of element e of a thread's direct load / store in round r (window win(r), pass offset s0), as seen by the
@@ -546,7 +588,9 @@ NTT_HD bool layout_here(const PassArgs<Cfg> &a, bool want) {
 template <class Cfg>
 NTT_HD uint32_t elem_off(const PassArgs<Cfg> &a, int e, bool want, int r) {
     const int sh = Cfg::win(r) + a.s0;
-    if constexpr (Cfg::LOG_E == 4) {
+    if constexpr (Cfg::MAT) {  // natural order only; sh >= s0 >= mat_w: whole rows
+        return ((uint32_t) e << (sh - a.mat_w)) * a.mat_pitch;
+    } else if constexpr (Cfg::LOG_E == 4) {
         return (layout_here<Cfg>(a, want) ? aie_block16((uint32_t) e) : (uint32_t) e) << sh;
     } else if constexpr (radix8_layout<Cfg>()) {
         if (layout_here<Cfg>(a, want)) {
@@ -1350,11 +1394,12 @@ NTT_HD void phase_cinv_scale(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
 // subtraction wraps and the minimum is the input itself, so the host model may run it unconditionally.
 template <class Cfg>
 NTT_HD void phase_canon(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
-    if constexpr (std::is_same<typename Cfg::F, FieldGL>::value && Cfg::INV && Cfg::CONTIG && Cfg::E >= 4) {
+    if constexpr (std::is_same<typename Cfg::F, FieldGL>::value && Cfg::INV && (Cfg::CONTIG || Cfg::MAT) && Cfg::E >= 4) {
         // Goldilocks inverse (DIT) butterflies keep sums and differences as ANY 64-bit representative (their
         // other operand is always a canonical product); the scaled inverse ends with a canonical product, the
         // unscaled one is canonicalised here: x >= p  <=>  x + (2^32 - 1) carries, and the wrapped sum is x - p.
         if (Cfg::CINV || a.do_scale) return;
+        if (Cfg::MAT && a.s0 != a.mat_w) return;  // a matrix transform ends in the column pass that holds stage 0
 #pragma unroll
         for (int e = 0; e < Cfg::E; ++e) {
             const uint64_t t = c.x[e] + 0xFFFFFFFFull;
@@ -1362,7 +1407,7 @@ NTT_HD void phase_canon(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
         }
     }
     if constexpr (std::is_same<typename Cfg::F, FieldM32>::value && Cfg::E >= 8) {
-        const bool last = Cfg::INV ? Cfg::CONTIG : (a.s0 + Cfg::LOG_M == a.n);
+        const bool last = Cfg::INV ? (Cfg::MAT ? a.s0 == a.mat_w : Cfg::CONTIG) : (a.s0 + Cfg::LOG_M == a.n);
         if (a.field.p >= 0x40000000u || !last || Cfg::CINV || (Cfg::INV && a.do_scale)) return;
 #pragma unroll
         for (int e = 0; e < Cfg::E; ++e) {

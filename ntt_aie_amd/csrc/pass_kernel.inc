@@ -129,6 +129,7 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
     // refused here before anything else, and again by the fill below, which the host index model shares
     if ((e.lde_beta != 0) != Cfg::LDE) return hipErrorInvalidValue;
     if ((e.cinv_u != nullptr) != Cfg::CINV) return hipErrorInvalidValue;  // ... likewise the coset interpolation's vector (PassCfg::CINV)
+    if ((e.mat_w != 0 || e.mat_pitch != 0 || e.mat_width != 0) != Cfg::MAT) return hipErrorInvalidValue;  // ... and the matrix addressing (PassCfg::MAT)
     PassGeom g = pass_geometry_of<Cfg>(e);
 #if defined(NTT_EXPERIMENT)
     if ((e.dbg & 0x1000) && g.grid_x == 1 && g.ppw == 1) {
@@ -151,7 +152,8 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
         const uint64_t slice = ((uint64_t) 65535u * (uint32_t) g.ppw) << g.log_up;
         for (uint64_t done = 0; done < e.batch; done += slice) {
             ErasedArgs sub = e;
-            const size_t off = (size_t) ((done << e.n) * sizeof(W));
+            // (matrices: a slice of `done` matrices of N * pitch words each; the compact LDE source below does not exist there)
+            const size_t off = (size_t) ((Cfg::MAT ? done * mat_words(e) : done << e.n) * sizeof(W));
             sub.in = (const char *) e.in + off;
             sub.out = (char *) e.out + off;
             if (e.in2) sub.in2 = (const char *) e.in2 + off;
@@ -183,5 +185,14 @@ hipError_t launch_pass_of(bool contig, int log_m, const ErasedArgs &a, hipStream
     return err;
 }
 template hipError_t launch_pass_of<NTT_FIELD, NTT_INV>(bool, int, const ErasedArgs &, hipStream_t);
+
+// ... and the matrix twin of the column pass that launch.h's mat_dispatch selects (ntt_forward_columns / ntt_inverse_columns)
+template <class F, bool INV>
+hipError_t launch_mat_of(int log_m, const ErasedArgs &a, hipStream_t s) {
+    hipError_t err = hipErrorInvalidValue;
+    if (!mat_dispatch<F, INV>(log_m, [&](auto tag) { err = launch_cfg<typename decltype(tag)::Cfg>(a, s); })) return hipErrorInvalidValue;
+    return err;
+}
+template hipError_t launch_mat_of<NTT_FIELD, NTT_INV>(int, const ErasedArgs &, hipStream_t);
 
 }  // namespace ntt

@@ -113,6 +113,23 @@ inline std::vector<PassDesc> plan_passes(int n, int word_bytes = 8) {
     return v;
 }
 
+// Row-major matrices (ntt_forward_columns / ntt_inverse_columns): ALL logn stages as column passes -- there is no contiguous
+// polynomial to run a CONTIG pass on.  The fewest passes of MIN_COL_LOG_M .. MAX_COL_LOG_M stages, split evenly, the longer ones
+// first: 16 = 8 + 8, 12 = 6 + 6, 17 = 6 + 6 + 5, 9 = 5 + 4.  (The 9-stage wide tile stays with the N = 2^22 plan.)  The even split
+// is a starting rule, not a measured optimum.  Empty below four stages: no column kernel shape exists there.
+inline std::vector<PassDesc> plan_column_passes(int n) {
+    std::vector<PassDesc> v;
+    if (n < MIN_COL_LOG_M) return v;
+    const int P = (n + MAX_COL_LOG_M - 1) / MAX_COL_LOG_M;
+    int s0 = 0;
+    for (int i = 0; i < P; i++) {
+        const int m = (n - s0 + (P - i) - 1) / (P - i);
+        v.push_back({false, s0, m});
+        s0 += m;
+    }
+    return v;
+}
+
 // ---- plan alternatives: the decomposition is chosen at LAUNCH, by batch size, among candidates fixed at plan creation by
 // (N, word size, modulus class).  The twiddle tables are direction- and split-agnostic (a pass addresses T by stage and
 // block), so an alternative costs no device memory.  What the reference does with its one knob: the slab size follows

@@ -178,6 +178,13 @@ class NTTPlan:
         return bool(_lib.lib().ntt_plan_info(self._h, 12))
 
     @property
+    def column_passes(self) -> list[tuple[int, int]]:
+        """[(first stage, stages)] of the column passes forward_columns() / inverse_columns() run (ntt_plan_info 13 / 128+ / 96+);
+        empty when logn < 4, where no column kernel shape exists."""
+        L = _lib.lib()
+        return [(int(L.ntt_plan_info(self._h, 128 + i)), int(L.ntt_plan_info(self._h, 96 + i))) for i in range(int(L.ntt_plan_info(self._h, 13)))]
+
+    @property
     def has_inverse(self) -> bool:
         return bool(_lib.lib().ntt_plan_info(self._h, 4))
 
@@ -265,6 +272,76 @@ class NTTPlan:
         check(_lib.lib().ntt_inverse(self._h, inp.data_ptr(), out.data_ptr(), b, layout, int(scale),
                                      self._stream(stream)), "ntt_inverse")
         return out
+
+    # ---- row-major matrices: every column of [N][width] is a polynomial -------------
+    def _matrix(self, t: torch.Tensor, what: str) -> tuple[int, int, int]:
+        """(width, pitch, count) of a matrix view the C-ABI can address: [N][width] or [count][N][width], last stride 1, row stride =
+        pitch >= width, matrix stride = N * pitch."""
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError("%s is not on cuda:%d" % (what, self.device))
+        if t.element_size() != self.word_bytes:
+            raise ValueError("%s must hold %d-byte words" % (what, self.word_bytes))
+        if t.dim() not in (2, 3) or t.shape[-2] != self.n:
+            raise ValueError("%s must be [N][width] or [count][N][width] with N = %d rows" % (what, self.n))
+        width, count = int(t.shape[-1]), (int(t.shape[0]) if t.dim() == 3 else 1)
+        if width == 0 or count == 0:
+            return width, width, count
+        pitch = int(t.stride(-2))
+        if width > 1 and t.stride(-1) != 1:
+            raise ValueError("%s: the last stride must be 1 (columns of a row are adjacent words)" % what)
+        if pitch < width:
+            raise ValueError("%s: the row stride (pitch) must be >= width" % what)
+        if t.dim() == 3 and count > 1 and t.stride(0) != self.n * pitch:
+            raise ValueError("%s: the matrix stride must be N * pitch = %d words" % (what, self.n * pitch))
+        return width, pitch, count
+
+    def _columns(self, fn, name: str, mat: torch.Tensor, out: torch.Tensor | None, stream, *extra) -> torch.Tensor:
+        width, pitch, count = self._matrix(mat, "mat")
+        if out is None:
+            if stream is None:
+                out = torch.empty(mat.shape, dtype=mat.dtype, device=mat.device)
+            else:  # allocated under the launch stream, as _out_like does
+                st = stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream), device=mat.device)
+                with torch.cuda.stream(st):
+                    out = torch.empty(mat.shape, dtype=mat.dtype, device=mat.device)
+        if out is not mat:
+            if tuple(out.shape) != tuple(mat.shape):
+                raise ValueError("out must have the shape of mat")
+            w2, p2, c2 = self._matrix(out, "out")
+            if width and count and p2 != pitch:
+                raise ValueError("out must have the pitch of mat (%d words), or be allocated by the call" % pitch)
+        check(fn(self._h, mat.data_ptr(), out.data_ptr(), width, pitch, count, *extra, self._stream(stream)), name)
+        return out
+
+    def forward_columns(self, mat: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """forward() on every COLUMN of the row-major matrix (or matrices) `mat`, where it lies (ntt_forward_columns): [N][width] or
+        [count][N][width], natural order; a strided view such as big[:, :, :width] is taken as it is, and words outside it are neither
+        read nor written.  `out=mat` transforms in place, and `out=` a tensor of mat's shape and pitch is written by the first pass: neither
+        costs a copy.  `out=None` allocates a contiguous result; for a contiguous `mat` that is free as well, but for a STRIDED view it
+        first copies the live words into the result (one extra trip of the matrix through HBM, what this entry point exists to avoid:
+        the C-ABI takes one pitch for both buffers) and transforms them there.  Pass `out=mat`, or an `out` of mat's pitch, to avoid it."""
+        if out is None and not mat.is_contiguous():
+            return self._columns_to_contiguous(_lib.lib().ntt_forward_columns, "ntt_forward_columns", mat, stream)
+        return self._columns(_lib.lib().ntt_forward_columns, "ntt_forward_columns", mat, out, stream)
+
+    def inverse_columns(self, mat: torch.Tensor, out: torch.Tensor | None = None, scale: bool = True, stream=None) -> torch.Tensor:
+        """inverse(scale=...) on every column of `mat` (ntt_inverse_columns); buffers as for forward_columns(), the extra copy of a strided
+        `mat` with `out=None` included."""
+        if out is None and not mat.is_contiguous():
+            return self._columns_to_contiguous(_lib.lib().ntt_inverse_columns, "ntt_inverse_columns", mat, stream, int(scale))
+        return self._columns(_lib.lib().ntt_inverse_columns, "ntt_inverse_columns", mat, out, stream, int(scale))
+
+    def _columns_to_contiguous(self, fn, name: str, mat: torch.Tensor, stream, *extra) -> torch.Tensor:
+        """A strided view in, a fresh contiguous result out: the C-ABI takes ONE pitch for both buffers, so the live words are copied
+        into the result under the launch stream and transformed in place there."""
+        self._matrix(mat, "mat")
+        st = None if stream is None else (stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream), device=mat.device))
+        if st is None:
+            out = mat.contiguous()
+        else:
+            with torch.cuda.stream(st):
+                out = mat.contiguous()
+        return self._columns(fn, name, out, out, stream, *extra)
 
     def coset_inverse(self, inp: torch.Tensor, out: torch.Tensor | None = None, layout: int = LAYOUT_NATURAL, stream=None) -> torch.Tensor:
         """Coset interpolation (ntt_coset_inverse): the scaled inverse of every row of `inp` (given in `layout`), word i times
