@@ -250,10 +250,48 @@ int ntt_coset_inverse(ntt_plan_t plan, const void *d_in, void *d_out, size_t bat
  * every index rule a size-2^28 transform obeys covers this one too.  NTT_E_LOGN: a plan with logn < 4 -- no column kernel
  * shape exists below four stages, and a prover has no such trace.  NTT_E_NOTABLE / NTT_E_NOTINVERTIBLE as for ntt_forward /
  * ntt_inverse.
- * Not provided: other layouts (both entry points are natural order only), a coset shift on columns, multi-device plans. */
+ * Not provided: other layouts (both entry points are natural order only), multi-device plans.  The coset operations on columns
+ * follow the next prototypes. */
 int ntt_forward_columns(ntt_plan_t plan, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, void *stream);
 int ntt_inverse_columns(ntt_plan_t plan, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, int scale,
                         void *stream);
+
+/* ---- coset LDE and coset interpolation on the columns of row-major matrices (no reference counterpart) ----
+ * ntt_lde and ntt_coset_inverse for the trace layout of the section above: a prover round on [N][width] with no transpose and no
+ * expanded, zero-filled intermediate.  No new plan state: ntt_lde_columns uses the setting and vector of ntt_plan_set_coset,
+ * ntt_coset_inverse_columns those of ntt_plan_set_coset_inverse; ntt_plan_clone copies both.  Defined at network level, for any
+ * (invertible) table and all three word classes.
+ *
+ * ntt_lde_columns.  M = 2^logn of the plan, beta the log_blowup of ntt_plan_set_coset, N = M >> beta.  d_in is `count` matrices
+ * [N][in_pitch], d_out `count` matrices [M][out_pitch], the first `width` columns of each are live (width <= both pitches).  Column
+ * c of output matrix m is exactly what ntt_lde(..., NTT_LAYOUT_NATURAL) gives on column c of input matrix m laid out contiguously:
+ *     Forward_M(x),  x[i << beta] = d_in[(m * N + i) * in_pitch + c] * s[i] mod p,  every other word of x zero.
+ * Out of place only: any overlap of the two byte ranges is NTT_E_ARG, d_in == d_out included.  The first executed pass reads d_in
+ * and writes d_out, the other passes run in place on d_out; nothing of size M is read or written before the first pass's own
+ * store.  In that pass a thread's 16 words are 16 consecutive rows of one column of which every 2^beta-th is live: it loads those
+ * from row (row >> beta) of the compact matrix, multiplies by s[row >> beta] -- the multiplier depends on the ROW only -- and keeps
+ * the others as zeros in registers.  Every first column pass has at least 4 stages >= beta, so there is no unfused fallback.
+ * With kind-1 tables and d_in = ntt_inverse_columns (scaled) of the size-N plan on the trace, row k of d_out holds the values at
+ * shift * w_M^k of every column: ready to hash ("Row-major trace").
+ *
+ * ntt_coset_inverse_columns.  Column c of the output is what ntt_coset_inverse(..., NTT_LAYOUT_NATURAL) gives on that column: row r
+ * of InvScaled_M is multiplied by shift^(-bitrev_logM(r)).  The multiplication happens in the last executed pass (the one that
+ * holds stage 0), just before its store, where ntt_inverse_columns(scale = 1) multiplies by the constant M^-1.  d_in == d_out is
+ * allowed; any other overlap is NTT_E_ARG, as in ntt_inverse_columns.
+ *
+ * Footprint, launch and alignment are those of ntt_forward_columns: only words with c < width are touched, input padding may hold
+ * non-canonical junk, output padding keeps its contents; buffers of exactly (count * rows - 1) * pitch + width words are sufficient,
+ * rows = N for the input of ntt_lde_columns and M everywhere else; asynchronous, no allocation, no host synchronisation;
+ * count == 0 or width == 0 is NTT_OK.
+ * Errors (existing codes only).  NTT_E_ARG: null plan, null or misaligned pointer, width greater than a pitch, forbidden overlap,
+ * count >= 2^31, no coset set (ntt_lde_columns) or no coset-inverse shift set (ntt_coset_inverse_columns), or the size rule of the
+ * section above applied to the M-row matrix: M * pitch <= 2^NTT_MAX_LOGN words and logn + w <= NTT_MAX_LOGN (the compact source
+ * obeys it with its own row count: N * in_pitch <= 2^NTT_MAX_LOGN words).  NTT_E_LOGN: logn < 4.  NTT_E_NOTABLE /
+ * NTT_E_NOTINVERTIBLE as for ntt_forward_columns / ntt_inverse_columns.
+ * Not provided: other layouts, multi-device plans. */
+int ntt_lde_columns(ntt_plan_t plan, const void *d_in, size_t in_pitch, void *d_out, size_t out_pitch, size_t width, size_t count,
+                    void *stream);
+int ntt_coset_inverse_columns(ntt_plan_t plan, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, void *stream);
 
 /* Profiling twin of ntt_forward (the reference brackets one kernel iteration with
  * trace events, src/aie_core.cc:129-131, src/aie2.py:168,316): identical launches

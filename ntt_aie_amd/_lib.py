@@ -36,6 +36,7 @@ EXPORTS = (
     "ntt_version", "ntt_error_string", "ntt_device_count", "ntt_plan_create", "ntt_plan_destroy",
     "ntt_plan_set_twiddles", "ntt_make_roots", "ntt_make_table", "ntt_plan_generate_twiddles", "ntt_plan_get_twiddles", "ntt_plan_info", "ntt_plan_select", "ntt_plan_set_policy", "ntt_plan_clone", "ntt_forward",
     "ntt_plan_set_coset", "ntt_lde", "ntt_plan_set_coset_inverse", "ntt_coset_inverse", "ntt_forward_columns", "ntt_inverse_columns",
+    "ntt_lde_columns", "ntt_coset_inverse_columns",
     "ntt_forward_profile", "ntt_inverse", "ntt_pointwise_mul", "ntt_polymul_negacyclic", "ntt_count_noncanonical", "ntt_forward_stages",
 )
 
@@ -89,6 +90,9 @@ def open_library(path: str, since_v3: bool = True) -> C.CDLL:
     if hasattr(L, "ntt_forward_columns"):
         L.ntt_forward_columns.argtypes = [vp, vp, vp, sz, sz, sz, vp]
         L.ntt_inverse_columns.argtypes = [vp, vp, vp, sz, sz, sz, C.c_int, vp]
+    if hasattr(L, "ntt_lde_columns"):
+        L.ntt_lde_columns.argtypes = [vp, vp, sz, vp, sz, sz, sz, vp]
+        L.ntt_coset_inverse_columns.argtypes = [vp, vp, vp, sz, sz, sz, vp]
     L.ntt_forward_profile.argtypes = [vp, vp, vp, sz, C.c_int, vp, C.POINTER(C.c_float), C.c_int,
                                       C.POINTER(C.c_int)]
     L.ntt_inverse.argtypes = [vp, vp, vp, sz, C.c_int, C.c_int, vp]

@@ -64,6 +64,15 @@ struct ErasedArgs {
     int mat_w;            // column pass over row-major matrices (ntt_*_columns; PassArgs::mat_*): log2 virtual row length / row pitch /
     uint32_t mat_pitch;   // live columns.  n and s0 are then the virtual polynomial's, batch counts matrices.  All zero: an ordinary
     uint32_t mat_width;   // launch
+    // The coset twins of the matrix pass (PassCfg::MLDE / MCINV) have operands of their own here -- lde_* and cinv_u above stay "off" in
+    // every matrix launch, they select CONTIG kernels -- and share the PassArgs fields: the first pass of ntt_lde_columns reads the compact
+    // source mat_lde_in (row pitch mat_src_pitch) times the coset vector mat_lde_s, blow-up 2^mat_lde_beta (0: not such a launch); the
+    // last pass of ntt_coset_inverse_columns multiplies row r by mat_cinv_u[r] (null: not such a launch)
+    const void *mat_lde_in;
+    const void *mat_lde_s;
+    int mat_lde_beta;
+    uint32_t mat_src_pitch;
+    const void *mat_cinv_u;
 #if defined(NTT_PHASE_STAMPS)
     void *stamps;            // diagnostic build: PassArgs::stamps / stamp_records (ntt_stamps_set)
     uint32_t stamp_records;
@@ -160,17 +169,40 @@ bool mat_dispatch(int log_m, Fn &&fn) {
     return with_log_m<host::MIN_COL_LOG_M, host::MAX_COL_LOG_M>(log_m, [&](auto m) { fn(CfgTag<ColMatCfg<F, decltype(m)::value, INV>>{}); });
 }
 
+// ... and its coset twins (pass.h: ColMatLdeCfg / ColMatCinvCfg), named by the launch's own operands: the fused expansion of
+// ntt_lde_columns (a.mat_lde_beta != 0, forward only), the per-row output scaling of ntt_coset_inverse_columns (a.mat_cinv_u, inverse only).
+// The rule of every matrix launch of the library; a launch without those operands gets the plain twin, exactly as mat_dispatch names it.
+template <class F, bool INV, class Fn>
+bool mat_twin_dispatch(int log_m, const ErasedArgs &a, Fn &&fn) {
+    if (a.mat_lde_beta != 0 && a.mat_cinv_u != nullptr) return false;
+    if (a.mat_lde_beta != 0) {
+        if constexpr (INV) return false;
+        else return with_log_m<host::MIN_COL_LOG_M, host::MAX_COL_LOG_M>(log_m, [&](auto m) { fn(CfgTag<ColMatLdeCfg<F, decltype(m)::value>>{}); });
+    }
+    if (a.mat_cinv_u != nullptr) {
+        if constexpr (INV) return with_log_m<host::MIN_COL_LOG_M, host::MAX_COL_LOG_M>(log_m, [&](auto m) { fn(CfgTag<ColMatCinvCfg<F, decltype(m)::value>>{}); });
+        else return false;
+    }
+    return mat_dispatch<F, INV>(log_m, fn);
+}
+
 // Largest matrix (N * pitch words) and virtual polynomial a matrix launch takes: those of a size-2^28 transform, so that every
 // 32-bit lane / element byte offset a column pass forms stays where it is for the largest ordinary plan (NTT_MAX_LOGN)
 constexpr int MAT_MAX_LOG_WORDS = 28;
 inline uint64_t mat_words(const ErasedArgs &e) { return e.n >= e.mat_w && e.n - e.mat_w < 32 ? ((uint64_t) 1 << (e.n - e.mat_w)) * e.mat_pitch : ~(uint64_t) 0; }
+// words of one compact source matrix of an MLDE launch (0 for every other launch)
+inline uint64_t mat_src_words(const ErasedArgs &e) {
+    return e.mat_lde_beta > 0 && e.n >= e.mat_w + e.mat_lde_beta && e.n - e.mat_w < 32 ? ((uint64_t) 1 << (e.n - e.mat_w - e.mat_lde_beta)) * e.mat_src_pitch : 0;
+}
 // Unit slots of a MAT workgroup that are used.  A small matrix leaves room for several per workgroup (log_up > 0), whose lane
 // offsets reach 2^log_up * N * pitch words whatever the width: no more matrices share a workgroup than keep that within
 // 2^MAT_MAX_LOG_WORDS; lanes of the slots beyond are dead (pass.h: Ctx::live).
 inline int mat_log_u(const ErasedArgs &e, int log_m, int log_c, int log_u) {
     const int one_matrix = (e.s0 - log_c) + (e.n - e.s0 - log_m);  // log2 units of one matrix
     int k = 0;
-    while (one_matrix + k < log_u && (mat_words(e) << (k + 1)) <= ((uint64_t) 1 << MAT_MAX_LOG_WORDS)) ++k;
+    // (an MLDE launch forms the same lane offsets into its compact source: both matrices obey the limit)
+    const uint64_t words = mat_words(e) > mat_src_words(e) ? mat_words(e) : mat_src_words(e);
+    while (one_matrix + k < log_u && (words << (k + 1)) <= ((uint64_t) 1 << MAT_MAX_LOG_WORDS)) ++k;
     return one_matrix + k < log_u ? one_matrix + k : log_u;
 }
 
@@ -233,6 +265,22 @@ bool fill_pass_args(const ErasedArgs &e, const PassGeom &g, PassArgs<Cfg> &a) {
         a.mat_w = e.mat_w;
         a.mat_pitch = e.mat_pitch;
         a.mat_width = e.mat_width;
+    }
+    // ... and the coset twins of the matrix pass: their operands are refused on any other configuration, a twin is refused without
+    // them, on a pass that does not hold stage 0 (s0 != mat_w), and -- the scaling twin, whose vector contains N^-1 -- as a scaled launch
+    if ((e.mat_lde_beta != 0 || e.mat_lde_in || e.mat_lde_s || e.mat_src_pitch != 0) != Cfg::MLDE) return false;
+    if constexpr (Cfg::MLDE) {
+        if (e.mat_lde_beta < 1 || e.mat_lde_beta > 4 || e.mat_lde_beta >= e.n - e.mat_w || e.s0 != e.mat_w || !e.mat_lde_in || !e.mat_lde_s) return false;
+        if (e.mat_width > e.mat_src_pitch || mat_src_words(e) > ((uint64_t) 1 << MAT_MAX_LOG_WORDS)) return false;
+        a.lde_in = (const W *) e.mat_lde_in;
+        a.lde_s = (const W *) e.mat_lde_s;
+        a.lde_beta = e.mat_lde_beta;
+        a.mat_src_pitch = e.mat_src_pitch;
+    }
+    if ((e.mat_cinv_u != nullptr) != Cfg::MCINV) return false;
+    if constexpr (Cfg::MCINV) {
+        if (e.s0 != e.mat_w || e.do_scale) return false;
+        a.cinv_u = (const W *) e.mat_cinv_u;
     }
     if constexpr (fold_scale<Cfg>()) {
         if (e.do_scale && e.tw_sc == nullptr) return false;  // these kernels have no scaling sweep

@@ -312,10 +312,14 @@ int run_inverse(ntt_plan *pl, const void *d_in, void *d_out, size_t batch, int l
 
 // ntt_forward_columns / ntt_inverse_columns: count matrices [N][pitch], the first `width` words of a row are live.  Every stage is a
 // column pass over the virtual polynomial of 2^(logn + w) words (pass.h: PassCfg::MAT), w = max(LOG_C, ceil_log2(width)).
-int run_columns(ntt_plan *pl, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, bool inverse, int scale, void *stream) {
+// ntt_lde_columns (COL_LDE) and ntt_coset_inverse_columns (COL_CINV) are the same loop with the coset twin in the pass that holds
+// stage 0 (pass.h: PassCfg::MLDE / MCINV): the LDE reads a compact [N >> beta][in_pitch] source there and is out of place only.
+enum ColKind { COL_PLAIN = 0, COL_LDE = 1, COL_CINV = 2 };
+int run_columns(ntt_plan *pl, ColKind kind, const void *d_in, size_t in_pitch, void *d_out, size_t pitch, size_t width, size_t count, bool inverse,
+                int scale, void *stream) {
     if (!pl) return NTT_E_ARG;
     if (pl->logn < MIN_COL_LOG_M) return NTT_E_LOGN;  // no column kernel shape below four stages
-    if (width > pitch) return NTT_E_ARG;
+    if (width > pitch || width > in_pitch) return NTT_E_ARG;
     const bool empty = count == 0 || width == 0;
     if (!empty) {
         if (!d_in || !d_out) return NTT_E_ARG;
@@ -323,25 +327,33 @@ int run_columns(ntt_plan *pl, const void *d_in, void *d_out, size_t width, size_
     }
     if (!pl->has_table) return NTT_E_NOTABLE;
     if (inverse && !pl->has_inv) return NTT_E_NOTINVERTIBLE;
+    if (kind == COL_LDE && pl->lde_beta == 0) return NTT_E_ARG;  // ntt_plan_set_coset first
+    if (kind == COL_CINV && !pl->cinv_set) return NTT_E_ARG;     // ntt_plan_set_coset_inverse first
     if (empty) return NTT_OK;
-    // size rule: N * pitch <= 2^NTT_MAX_LOGN words and logn + w <= NTT_MAX_LOGN -- what a size-2^28 transform obeys
+    // size rule: N * pitch <= 2^NTT_MAX_LOGN words and logn + w <= NTT_MAX_LOGN -- what a size-2^28 transform obeys; the compact
+    // source of the LDE obeys it with its own, smaller, row count
+    const int beta = kind == COL_LDE ? pl->lde_beta : 0;
     int w = ntt::col_log_c(pl->word_bytes);
     while (((size_t) 1 << w) < width && w < NTT_MAX_LOGN) ++w;
     if (pl->logn + w > NTT_MAX_LOGN || pitch > ((size_t) 1 << (NTT_MAX_LOGN - pl->logn)) || count > 0x7FFFFFFFull) return NTT_E_ARG;
-    const size_t N = (size_t) 1 << pl->logn;
-    if (count > (SIZE_MAX / 16) / (N * pitch)) return NTT_E_ARG;
-    const size_t foot = ((count * N - 1) * pitch + width) * (size_t) pl->word_bytes;  // bytes from the first to the last live word
+    if (in_pitch > ((size_t) 1 << (NTT_MAX_LOGN - pl->logn + beta))) return NTT_E_ARG;
+    const size_t N = (size_t) 1 << pl->logn, N_in = N >> beta;
+    if (count > (SIZE_MAX / 16) / (N * pitch) || count > (SIZE_MAX / 16) / (N_in * in_pitch)) return NTT_E_ARG;
+    // bytes from the first to the last live word of each buffer
+    const size_t foot_in = ((count * N_in - 1) * in_pitch + width) * (size_t) pl->word_bytes;
+    const size_t foot_out = ((count * N - 1) * pitch + width) * (size_t) pl->word_bytes;
     const uintptr_t in0 = (uintptr_t) d_in, out0 = (uintptr_t) d_out;
-    if (in0 != out0 && in0 < out0 + foot && out0 < in0 + foot) return NTT_E_ARG;  // in place, or apart
+    if ((kind == COL_LDE || in0 != out0) && in0 < out0 + foot_out && out0 < in0 + foot_in) return NTT_E_ARG;  // in place (not the LDE), or apart
     DeviceGuard g(pl->device);
     if (g.err != hipSuccess) return (int) g.err;
     hipStream_t s = (hipStream_t) stream;
-    RoctxRange whole(inverse ? "ntt_inverse_columns" : "ntt_forward_columns");
+    static const char *const names[3][2] = {{"ntt_forward_columns", "fwd columns pass"}, {"ntt_lde_columns", "lde columns pass"}, {"ntt_coset_inverse_columns", "coset inv columns pass"}};
+    RoctxRange whole(kind == COL_PLAIN && inverse ? "ntt_inverse_columns" : names[kind][0]);
     const std::vector<PassDesc> &passes = pl->col_passes;
     const void *src = d_in;
     for (size_t k = 0; k < passes.size(); k++) {
         const PassDesc &pd = passes[inverse ? passes.size() - 1 - k : k];
-        RoctxRange pass(inverse ? "inv columns pass" : "fwd columns pass", 0, pd.s0, pd.log_m);
+        RoctxRange pass(kind == COL_PLAIN && inverse ? "inv columns pass" : names[kind][1], 0, pd.s0, pd.log_m);
         ntt::ErasedArgs a = base_args(pl, pd, src, d_out, count);
         a.n = pl->logn + w;
         a.s0 = pd.s0 + w;
@@ -352,6 +364,14 @@ int run_columns(ntt_plan *pl, const void *d_in, void *d_out, size_t width, size_
         a.layout = NTT_LAYOUT_NATURAL;
         a.do_scale = (inverse && scale && pd.s0 == 0) ? 1 : 0;  // the sweep of the last executed pass, the one that holds stage 0
         a.scale = pl->scale_tf;
+        if (kind == COL_LDE && pd.s0 == 0) {  // the first executed pass: compact source in, expanded tile out (`in` is not read)
+            a.in = d_out;
+            a.mat_lde_in = d_in;
+            a.mat_lde_s = pl->d_lde_s;
+            a.mat_lde_beta = beta;
+            a.mat_src_pitch = (uint32_t) in_pitch;
+        }
+        if (kind == COL_CINV && pd.s0 == 0) a.mat_cinv_u = pl->d_cinv_u;  // the last executed pass: N^-1 is inside the vector
         const hipError_t e = ntt::launch_mat_pass(inverse, pd.log_m, a, s);
         if (e != hipSuccess) return (int) e;
         src = d_out;
@@ -873,11 +893,19 @@ int ntt_inverse(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int 
 } NTT_GUARD_END
 
 int ntt_forward_columns(ntt_plan_t pl, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, void *stream) NTT_GUARD {
-    return run_columns(pl, d_in, d_out, width, pitch, count, false, 0, stream);
+    return run_columns(pl, COL_PLAIN, d_in, pitch, d_out, pitch, width, count, false, 0, stream);
 } NTT_GUARD_END
 
 int ntt_inverse_columns(ntt_plan_t pl, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, int scale, void *stream) NTT_GUARD {
-    return run_columns(pl, d_in, d_out, width, pitch, count, true, scale, stream);
+    return run_columns(pl, COL_PLAIN, d_in, pitch, d_out, pitch, width, count, true, scale, stream);
+} NTT_GUARD_END
+
+int ntt_lde_columns(ntt_plan_t pl, const void *d_in, size_t in_pitch, void *d_out, size_t out_pitch, size_t width, size_t count, void *stream) NTT_GUARD {
+    return run_columns(pl, COL_LDE, d_in, in_pitch, d_out, out_pitch, width, count, false, 0, stream);
+} NTT_GUARD_END
+
+int ntt_coset_inverse_columns(ntt_plan_t pl, const void *d_in, void *d_out, size_t width, size_t pitch, size_t count, void *stream) NTT_GUARD {
+    return run_columns(pl, COL_CINV, d_in, pitch, d_out, pitch, width, count, true, 0, stream);
 } NTT_GUARD_END
 
 int ntt_coset_inverse(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int in_layout, void *stream) NTT_GUARD {

@@ -117,7 +117,8 @@ NTT_HD void static_for(Fn &&f) {
 }
 
 template <class F_, int LOG_M_, int LOG_C_, bool CONTIG_, bool INV_, int PRELOAD_MASK_ = 0xF, int LOG_E_ = 4,
-          int LOG_NT_ = LOG_NT, bool ALLOW_DMA_ = true, bool LDE_ = false, bool CINV_ = false, bool MAT_ = false>
+          int LOG_NT_ = LOG_NT, bool ALLOW_DMA_ = true, bool LDE_ = false, bool CINV_ = false, bool MAT_ = false, bool MLDE_ = false,
+          bool MCINV_ = false>
 struct PassCfg {
     using F = F_;
     using W = typename F::W;
@@ -204,6 +205,19 @@ struct PassCfg {
     // idx of the virtual view lives at (idx >> w) * pitch + (idx & (2^w - 1)) (mat_word), lanes whose column is >= width are dead.
     static constexpr bool MAT = MAT_;
     static_assert(!MAT_ || (!CONTIG_ && !LDE_ && !CINV_ && LOG_E_ == 4), "the matrix addressing lives in a (non-CONTIG) radix-16 column pass");
+    // MLDE_: the first pass of a coset low-degree extension on matrix columns (ntt_lde_columns), a twin of the forward MAT pass that
+    // holds stage 0 (s0 == mat_w: round 0's window is row bits 0..3).  Round 0's words are not read from `in`: element e of a thread
+    // is row (16 * k + e) of its column, live only when its low lde_beta bits are clear, and then it is word (row >> lde_beta) of the
+    // same column of the compact matrix [N >> lde_beta][mat_src_pitch] (PassArgs::lde_in) times the coset word of that ROW
+    // (PassArgs::lde_s) -- the other elements are zeros in registers.  No LDS scatter, no zero-fill, nothing of the big size is read.
+    static constexpr bool MLDE = MLDE_;
+    static_assert(!MLDE_ || (MAT_ && !INV_), "the fused expansion on columns lives in a forward matrix pass");
+    // MCINV_: the last executed pass of a coset interpolation on matrix columns (ntt_coset_inverse_columns), a twin of the inverse
+    // MAT pass that holds stage 0: the unscaled rounds, then every output word is multiplied by the word of PassArgs::cinv_u of its
+    // ROW (phase_cinv_scale: after round 0 a thread holds 16 consecutive rows of one column), where the scaled inverse multiplies by
+    // the constant N^-1 (phase_scale).
+    static constexpr bool MCINV = MCINV_;
+    static_assert(!MCINV_ || (MAT_ && INV_), "the per-row output scaling lives in an inverse matrix pass");
     static constexpr int LDS_WORDS = LDS_WORDS_PADDED;
     // Register prefetch of the NEXT polynomial's tile (round 6, BASELINE config 2): the 4-byte 512-thread radix-8 kernels that run a
     // single-pass size (PassDesc::variant 1) stage their tile linearly by ordinary loads; with PREFETCH a thread requests its E words
@@ -269,6 +283,12 @@ using ColPassCfg = PassCfg<F, LOG_M, col_log_c(sizeof(typename F::W)), false, IN
 // ... and its matrix twin (PassCfg::MAT): the same tile, rounds and workgroup, 4 .. 8 stages
 template <class F, int LOG_M, bool INV>
 using ColMatCfg = PassCfg<F, LOG_M, col_log_c(sizeof(typename F::W)), false, INV, 0xF, 4, col_log_nt(sizeof(typename F::W)), true, false, false, true>;
+// ... and the two coset twins of THAT (PassCfg::MLDE forward, PassCfg::MCINV inverse): the pass that holds stage 0 of ntt_lde_columns /
+// ntt_coset_inverse_columns
+template <class F, int LOG_M>
+using ColMatLdeCfg = PassCfg<F, LOG_M, col_log_c(sizeof(typename F::W)), false, false, 0xF, 4, col_log_nt(sizeof(typename F::W)), true, false, false, true, true, false>;
+template <class F, int LOG_M>
+using ColMatCinvCfg = PassCfg<F, LOG_M, col_log_c(sizeof(typename F::W)), false, true, 0xF, 4, col_log_nt(sizeof(typename F::W)), true, false, false, true, false, true>;
 
 // How the rows of blockIdx.y share the polynomial groups of the batch.  Rows [0, rows[0]) stream `ppw` groups each through
 // their resident twiddles; the next rows[1] rows ppw/2 each, then ppw/4, then ppw/8 (0 rows = level absent).  Rows are
@@ -320,6 +340,9 @@ struct PassArgs {
     int mat_w = 0;           // log2 of the virtual row length: max(LOG_C, ceil_log2(mat_width))
     uint32_t mat_pitch = 0;  // words between two rows of a matrix
     uint32_t mat_width = 0;  // columns that exist; a lane whose column is >= mat_width neither loads nor stores
+    // PassCfg::MLDE kernels only (zero for every other launch): words between two rows of the compact source matrix lde_in, which has
+    // (2^(n - mat_w)) >> lde_beta rows per matrix; lde_s and lde_beta as above, indexed by the compact ROW
+    uint32_t mat_src_pitch = 0;
 #if defined(NTT_PHASE_STAMPS)
     unsigned long long *stamps;  // [stamp_records][STAMP_RECORD] 64-bit slots, one record per wave of the launch (null: stamps go to a dummy record)
     uint32_t stamp_records;
@@ -373,6 +396,14 @@ NTT_HD uint32_t lane_word(const PassArgs<Cfg> &a, int b0, uint32_t q, uint32_t c
 template <class Cfg>
 NTT_HD uint32_t mat_word(const PassArgs<Cfg> &a, uint32_t idx) {
     return (idx >> a.mat_w) * a.mat_pitch + (idx & ((1u << a.mat_w) - 1u));
+}
+
+// PassCfg::MLDE: where word idx of the virtual view lives in the COMPACT source -- row (idx >> mat_w) >> lde_beta, column unchanged.
+// For terms whose row part is a multiple of 2^lde_beta: the tile's row origin, the matrix slot and the lane's q << LOG_E are multiples
+// of 16 rows >= 2^lde_beta, so the shift is exact term by term and the sum of the mapped terms is the mapped sum, as for mat_word.
+template <class Cfg>
+NTT_HD uint32_t mlde_word(const PassArgs<Cfg> &a, uint32_t idx) {
+    return ((idx >> a.mat_w) >> a.lde_beta) * a.mat_src_pitch + (idx & ((1u << a.mat_w) - 1u));
 }
 
 // uniform part of the word index: workgroup tile origin + polynomial group of iteration `it`
@@ -543,7 +574,8 @@ NTT_HD void phase_init(Ctx<Cfg> &c, const PassArgs<Cfg> &a, uint32_t tid, uint32
         const uint32_t ltb = bx & ((1u << log_ltb) - 1u);
         const uint32_t mcol = ((ltb << (a.log_ul + Cfg::LOG_C)) + (u_l << Cfg::LOG_C) + col) & ((1u << a.mat_w) - 1u);
         c.live = mcol < a.mat_width && (u >> (a.log_ul + a.log_uh + a.log_up)) == 0u;
-        c.lane_ld = mat_word<Cfg>(a, c.lane_ld);
+        if constexpr (Cfg::MLDE) c.lane_ld = mlde_word<Cfg>(a, c.lane_ld);  // the only load of this lane term is the compact source's
+        else c.lane_ld = mat_word<Cfg>(a, c.lane_ld);
         c.lane_st = mat_word<Cfg>(a, c.lane_st);
     }
     static_for<0, Cfg::R>([&](auto rr) {
@@ -688,9 +720,66 @@ NTT_HD void phase_load_direct_to(Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it, ty
 #endif
 }
 
+// ---- coset low-degree extension on matrix columns (Cfg::MLDE; ntt_lde_columns' first pass) ------------------------------------
+// uniform part of the compact source's word index: uniform_word() with every row term shifted right by lde_beta (s0 == mat_w: the hi
+// block and the matrix group are multiples of 2^LOG_M >= 16 rows; the lo-tile block is a column offset below 2^mat_w)
+template <class Cfg>
+NTT_HD size_t mlde_uniform_word(const Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it) {
+    const int log_ltb = a.s0 - Cfg::LOG_C - a.log_ul;
+    const uint32_t ltb = c.bx & ((1u << log_ltb) - 1u);
+    const uint32_t hb = c.bx >> log_ltb;
+    const size_t pg = (size_t) c.pg_base + (size_t) it * (uint32_t) a.pg_stride;
+    return ((((size_t) hb << (a.log_uh + Cfg::LOG_M)) + (pg << (a.log_up + a.n - a.mat_w))) >> a.lde_beta) * a.mat_src_pitch +
+           (size_t) (ltb << (a.log_ul + Cfg::LOG_C));
+}
+
+// round 0's words of iteration `it`: x[k << B] = compact word * coset word, zeros elsewhere (B = lde_beta, a compile-time copy per
+// value: which registers are zero is then known to the compiler).  After the load a thread holds rows (hi << LOG_M) + (q << LOG_E) + e
+// of its column (cinv_word), live ones at e = k << B, whose coset word is s[(first row >> B) + k]: one aligned run of E >> B words
+// that depends on the row only and ends at or before word 2^(n - mat_w - B), never past the vector.  The run is fetched from L2 every
+// iteration, as the scaling twin fetches its words of u: kept in registers across the batch loop (as Ctx::lde_s is) it took the
+// 8-byte kernels of 6 and 7 stages past 128 VGPRs (4 -> 3 waves per SIMD) and the 4-byte one of 8 stages from 6 to 5 waves.
+template <class Cfg, int B>
+NTT_HD void mlde_load(Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it) {
+    using W = typename Cfg::W;
+    const W *ubase = a.lde_in + mlde_uniform_word<Cfg>(c, a, it);
+    const W *s = a.lde_s + (((c.hi << Cfg::LOG_M) + (c.q << Cfg::LOG_E)) >> B);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *) ubase, 0, -1, 0x00020000);
+    const uint32_t voff = c.lane_ld * (uint32_t) sizeof(W);
+#endif
+#pragma unroll
+    for (int e = 0; e < Cfg::E; ++e) c.x[e] = (W) 0;
+#pragma unroll
+    for (int k = 0; k < (Cfg::E >> B); ++k) {
+        const uint32_t eo = (uint32_t) k * a.mat_src_pitch;  // element k << B is compact row k of the thread's run
+        if (c.active) {
+#if defined(__HIP_DEVICE_COMPILE__)
+            c.x[k << B] = buf_load<W>(rs, voff, eo * (uint32_t) sizeof(W));
+#else
+            c.x[k << B] = (ubase + (size_t) eo)[c.lane_ld];
+#endif
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < (Cfg::E >> B); ++k) c.x[k << B] = a.field.mul(c.x[k << B], s[k]);
+}
+template <class Cfg>
+NTT_HD void phase_mlde_load(Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it) {
+    if (a.lde_beta == 1) mlde_load<Cfg, 1>(c, a, it);  // uniform
+    else if (a.lde_beta == 2) mlde_load<Cfg, 2>(c, a, it);
+    else if (a.lde_beta == 3) mlde_load<Cfg, 3>(c, a, it);
+    else mlde_load<Cfg, 4>(c, a, it);
+}
+
 template <class Cfg, int r>
 NTT_HD void phase_load_direct(Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it) {
-    phase_load_direct_to<Cfg, r>(c, a, it, c.x, c.active);
+    if constexpr (Cfg::MLDE) {
+        static_assert(r == 0, "the fused expansion is the load of round 0");
+        phase_mlde_load<Cfg>(c, a, it);
+    } else {
+        phase_load_direct_to<Cfg, r>(c, a, it, c.x, c.active);
+    }
 }
 
 template <class Cfg, int r>
@@ -1398,7 +1487,7 @@ NTT_HD void phase_canon(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
         // Goldilocks inverse (DIT) butterflies keep sums and differences as ANY 64-bit representative (their
         // other operand is always a canonical product); the scaled inverse ends with a canonical product, the
         // unscaled one is canonicalised here: x >= p  <=>  x + (2^32 - 1) carries, and the wrapped sum is x - p.
-        if (Cfg::CINV || a.do_scale) return;
+        if (Cfg::CINV || Cfg::MCINV || a.do_scale) return;
         if (Cfg::MAT && a.s0 != a.mat_w) return;  // a matrix transform ends in the column pass that holds stage 0
 #pragma unroll
         for (int e = 0; e < Cfg::E; ++e) {
@@ -1408,7 +1497,7 @@ NTT_HD void phase_canon(Ctx<Cfg> &c, const PassArgs<Cfg> &a) {
     }
     if constexpr (std::is_same<typename Cfg::F, FieldM32>::value && Cfg::E >= 8) {
         const bool last = Cfg::INV ? (Cfg::MAT ? a.s0 == a.mat_w : Cfg::CONTIG) : (a.s0 + Cfg::LOG_M == a.n);
-        if (a.field.p >= 0x40000000u || !last || Cfg::CINV || (Cfg::INV && a.do_scale)) return;
+        if (a.field.p >= 0x40000000u || !last || Cfg::CINV || Cfg::MCINV || (Cfg::INV && a.do_scale)) return;
 #pragma unroll
         for (int e = 0; e < Cfg::E; ++e) {
             const uint32_t d = c.x[e] - a.field.p;
@@ -1520,7 +1609,7 @@ NTT_HD void run_pass(Exec &ex, const PassArgs<Cfg> &a) {
         // the unscaled kernel carries neither the sweep's code nor its 24 scratch registers)
         // (a coset interpolation runs the unscaled rounds and multiplies by its vector instead: N^-1 is inside the vector, and the
         // shared argument fill never hands such a kernel a scaled launch, so its SC form is never the one that runs)
-        if constexpr (Cfg::CINV) ex.each([&](C &c) { phase_cinv_scale<Cfg, M32_MODE>(c, a); });
+        if constexpr (Cfg::CINV || Cfg::MCINV) ex.each([&](C &c) { phase_cinv_scale<Cfg, M32_MODE>(c, a); });
         else if constexpr (Cfg::INV && !SC && !fold_scale<Cfg>()) ex.each([&](C &c) { phase_scale<Cfg, M32_MODE>(c, a); });
         ex.each([&](C &c) { phase_canon<Cfg>(c, a); });
         if constexpr (Cfg::DIRECT_STORE) {

@@ -99,8 +99,12 @@ struct GpuExec {
 #endif
 // SC: the scaled-inverse specialisation with N^-1 folded into stage 0 (pass.h: fold_scale) -- a kernel of its own, so that
 // its heavier last stage does not touch the register allocation of the unscaled one
+// (the fused expansion on columns keeps the occupancy bracket of the plain matrix pass it stands in for: 4 waves of 8-byte words, 6 of
+// 4-byte words -- left alone, the 8-stage kernel of general 8-byte words takes 129 VGPRs and the 6-stage one of 4-byte words 81.  The
+// 8-stage kernel of 4-byte words is the exception: it needs 87, held to 80 it spills 20 bytes, so it runs at 5 waves and no scratch)
 template <class Cfg, bool SC = false>
-__global__ __launch_bounds__(Cfg::NT, (Cfg::LOG_E < 4 && Cfg::LOG_M >= 7) ? NTT_E8_WPE
+__global__ __launch_bounds__(Cfg::NT, (Cfg::MLDE && !(sizeof(typename Cfg::W) == 4 && Cfg::LOG_M == 8)) ? (sizeof(typename Cfg::W) == 8 ? 4 : 6)
+                                 : (Cfg::LOG_E < 4 && Cfg::LOG_M >= 7) ? NTT_E8_WPE
                                  : (Cfg::CONTIG && Cfg::R == 3 && sizeof(typename Cfg::W) == 8) ? NTT_R3_WPE
                                  : (!Cfg::CONTIG && Cfg::LOG_M == 9 && sizeof(typename Cfg::W) == 8) ? NTT_COL9_WPE : 1)
 void pass_kernel(PassArgs<Cfg> a) {
@@ -130,6 +134,7 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
     if ((e.lde_beta != 0) != Cfg::LDE) return hipErrorInvalidValue;
     if ((e.cinv_u != nullptr) != Cfg::CINV) return hipErrorInvalidValue;  // ... likewise the coset interpolation's vector (PassCfg::CINV)
     if ((e.mat_w != 0 || e.mat_pitch != 0 || e.mat_width != 0) != Cfg::MAT) return hipErrorInvalidValue;  // ... and the matrix addressing (PassCfg::MAT)
+    if ((e.mat_lde_beta != 0) != Cfg::MLDE || (e.mat_cinv_u != nullptr) != Cfg::MCINV) return hipErrorInvalidValue;  // ... and its coset twins' operands (PassCfg::MLDE / MCINV)
     PassGeom g = pass_geometry_of<Cfg>(e);
 #if defined(NTT_EXPERIMENT)
     if ((e.dbg & 0x1000) && g.grid_x == 1 && g.ppw == 1) {
@@ -157,6 +162,7 @@ hipError_t launch_cfg(const ErasedArgs &e, hipStream_t s) {
             sub.in = (const char *) e.in + off;
             sub.out = (char *) e.out + off;
             if (e.in2) sub.in2 = (const char *) e.in2 + off;
+            if constexpr (Cfg::MLDE) sub.mat_lde_in = (const char *) e.mat_lde_in + (size_t) (done * mat_src_words(e) * sizeof(W));
             if (e.lde_beta) sub.lde_in = (const char *) e.lde_in + (off >> e.lde_beta);
             sub.batch = (uint32_t) (e.batch - done < slice ? e.batch - done : slice);
             const hipError_t err = launch_cfg<Cfg>(sub, s);
@@ -186,11 +192,12 @@ hipError_t launch_pass_of(bool contig, int log_m, const ErasedArgs &a, hipStream
 }
 template hipError_t launch_pass_of<NTT_FIELD, NTT_INV>(bool, int, const ErasedArgs &, hipStream_t);
 
-// ... and the matrix twin of the column pass that launch.h's mat_dispatch selects (ntt_forward_columns / ntt_inverse_columns)
+// ... and the matrix twin of the column pass that launch.h's mat_twin_dispatch selects (ntt_forward_columns / ntt_inverse_columns: the
+// plain twin mat_dispatch names; ntt_lde_columns / ntt_coset_inverse_columns: the coset twin of the pass that holds stage 0)
 template <class F, bool INV>
 hipError_t launch_mat_of(int log_m, const ErasedArgs &a, hipStream_t s) {
     hipError_t err = hipErrorInvalidValue;
-    if (!mat_dispatch<F, INV>(log_m, [&](auto tag) { err = launch_cfg<typename decltype(tag)::Cfg>(a, s); })) return hipErrorInvalidValue;
+    if (!mat_twin_dispatch<F, INV>(log_m, a, [&](auto tag) { err = launch_cfg<typename decltype(tag)::Cfg>(a, s); })) return hipErrorInvalidValue;
     return err;
 }
 template hipError_t launch_mat_of<NTT_FIELD, NTT_INV>(int, const ErasedArgs &, hipStream_t);

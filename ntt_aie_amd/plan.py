@@ -274,15 +274,17 @@ class NTTPlan:
         return out
 
     # ---- row-major matrices: every column of [N][width] is a polynomial -------------
-    def _matrix(self, t: torch.Tensor, what: str) -> tuple[int, int, int]:
+    def _matrix(self, t: torch.Tensor, what: str, rows: int | None = None) -> tuple[int, int, int]:
         """(width, pitch, count) of a matrix view the C-ABI can address: [N][width] or [count][N][width], last stride 1, row stride =
-        pitch >= width, matrix stride = N * pitch."""
+        pitch >= width, matrix stride = N * pitch.  `rows`: the row count where it is not the plan's N (the compact input of
+        lde_columns())."""
+        rows = self.n if rows is None else rows
         if not t.is_cuda or t.device.index != self.device:
             raise ValueError("%s is not on cuda:%d" % (what, self.device))
         if t.element_size() != self.word_bytes:
             raise ValueError("%s must hold %d-byte words" % (what, self.word_bytes))
-        if t.dim() not in (2, 3) or t.shape[-2] != self.n:
-            raise ValueError("%s must be [N][width] or [count][N][width] with N = %d rows" % (what, self.n))
+        if t.dim() not in (2, 3) or t.shape[-2] != rows:
+            raise ValueError("%s must be [N][width] or [count][N][width] with N = %d rows" % (what, rows))
         width, count = int(t.shape[-1]), (int(t.shape[0]) if t.dim() == 3 else 1)
         if width == 0 or count == 0:
             return width, width, count
@@ -291,8 +293,8 @@ class NTTPlan:
             raise ValueError("%s: the last stride must be 1 (columns of a row are adjacent words)" % what)
         if pitch < width:
             raise ValueError("%s: the row stride (pitch) must be >= width" % what)
-        if t.dim() == 3 and count > 1 and t.stride(0) != self.n * pitch:
-            raise ValueError("%s: the matrix stride must be N * pitch = %d words" % (what, self.n * pitch))
+        if t.dim() == 3 and count > 1 and t.stride(0) != rows * pitch:
+            raise ValueError("%s: the matrix stride must be N * pitch = %d words" % (what, rows * pitch))
         return width, pitch, count
 
     def _columns(self, fn, name: str, mat: torch.Tensor, out: torch.Tensor | None, stream, *extra) -> torch.Tensor:
@@ -342,6 +344,42 @@ class NTTPlan:
             with torch.cuda.stream(st):
                 out = mat.contiguous()
         return self._columns(fn, name, out, out, stream, *extra)
+
+    def lde_columns(self, mat: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """lde() on every COLUMN of the row-major matrix (or matrices) `mat` (ntt_lde_columns): [N][width] or [count][N][width] in,
+        N = M >> log_blowup rows in the order inverse_columns() of the size-N plan leaves them, strided views taken as they are;
+        [M][width] (or [count][M][width]) out.  `out=None` allocates a contiguous [count][M][width] (or [M][width]) result; an `out`
+        view may have any pitch of its own, and must not overlap `mat`.  Nothing of the big size is read or written before the first
+        pass's own store."""
+        beta = self.log_blowup
+        if beta == 0:
+            raise ValueError("set_coset() first")
+        n_small = self.n >> beta
+        width, in_pitch, count = self._matrix(mat, "mat", n_small)
+        shape = tuple(mat.shape[:-2]) + (self.n, width)
+        if out is None:
+            if stream is None:
+                out = torch.empty(shape, dtype=mat.dtype, device=mat.device)
+            else:  # allocated under the launch stream, as _out_like does
+                st = stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream), device=mat.device)
+                with torch.cuda.stream(st):
+                    out = torch.empty(shape, dtype=mat.dtype, device=mat.device)
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be %s for this mat" % (shape,))
+        _, out_pitch, _ = self._matrix(out, "out")
+        check(_lib.lib().ntt_lde_columns(self._h, mat.data_ptr(), in_pitch, out.data_ptr(), out_pitch, width, count, self._stream(stream)),
+              "ntt_lde_columns")
+        return out
+
+    def coset_inverse_columns(self, mat: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """coset_inverse() on every column of `mat` (ntt_coset_inverse_columns): [M][width] or [count][M][width]; buffers as for
+        inverse_columns(), the extra copy of a strided `mat` with `out=None` included.  With kind-1 tables and rows holding the values
+        at shift * w_M^k in, row j of the result holds coefficient bitrev_M(j) of every column: the order lde_columns() consumes."""
+        if not self.coset_inverse_set:
+            raise ValueError("set_coset_inverse() first")
+        if out is None and not mat.is_contiguous():
+            return self._columns_to_contiguous(_lib.lib().ntt_coset_inverse_columns, "ntt_coset_inverse_columns", mat, stream)
+        return self._columns(_lib.lib().ntt_coset_inverse_columns, "ntt_coset_inverse_columns", mat, out, stream)
 
     def coset_inverse(self, inp: torch.Tensor, out: torch.Tensor | None = None, layout: int = LAYOUT_NATURAL, stream=None) -> torch.Tensor:
         """Coset interpolation (ntt_coset_inverse): the scaled inverse of every row of `inp` (given in `layout`), word i times
