@@ -65,6 +65,43 @@ int emu_column_passes(int logn, int *s0, int *log_m, int cap) {
     return (int) v.size();
 }
 
+// The launch geometry of pass `pass` (an index into plan_column_passes(logn)) of a columns call on this shape, as the launchers form
+// it: mat_dispatch names the kernel, pass_geometry_of sizes its grid -- the launch.h code itself, no restatement.  geom: grid_x,
+// grid_y, ppw, log_up and the four taper rows.  0, -1 for a bad shape, -2 when there is no such pass or kernel
+int emu_columns_geometry(int word_bytes, uint64_t p, int logn, uint32_t width, uint32_t pitch, uint32_t count, uint32_t target_wgs, int pass,
+                         int inverse, uint32_t *geom) {
+    if (width == 0 || count == 0 || width > pitch) return -1;
+    const std::vector<PassDesc> passes = plan_column_passes(logn);
+    if (pass < 0 || (size_t) pass >= passes.size()) return -2;
+    const int log_c = col_log_c(word_bytes);
+    const int w = ceil_log2(width) > log_c ? ceil_log2(width) : log_c;
+    ErasedArgs e;
+    memset(&e, 0, sizeof(e));
+    e.field = field_params(word_bytes, p);
+    e.n = logn + w;
+    e.s0 = passes[pass].s0 + w;
+    e.batch = count;
+    e.layout = LAYOUT_NATURAL;
+    e.target_wgs = target_wgs;
+    e.mat_w = w;
+    e.mat_pitch = pitch;
+    e.mat_width = width;
+    int rc = -2;
+    auto report = [&](auto tag) {
+        const PassGeom g = pass_geometry_of<typename decltype(tag)::Cfg>(e);
+        const uint32_t v[8] = {g.grid_x, g.grid_y, (uint32_t) g.ppw, (uint32_t) g.log_up, g.tp.rows[0], g.tp.rows[1], g.tp.rows[2], g.tp.rows[3]};
+        memcpy(geom, v, sizeof(v));
+        rc = 0;
+    };
+    with_field(e.field, [&](auto f) {
+        using F = decltype(f);
+        if (inverse) mat_dispatch<F, true>(passes[pass].log_m, report);
+        else mat_dispatch<F, false>(passes[pass].log_m, report);
+        return 0;
+    });
+    return rc;
+}
+
 // One matrix transform as ntt_forward_columns / ntt_inverse_columns run it.  T_plain: the size-2^logn table, plain residues; in, out:
 // (count * 2^logn - 1) * pitch + width words (out may be in).
 int emu_columns(int word_bytes, int logn, uint64_t p, const void *T_plain, const void *in, void *out, uint32_t width, uint32_t pitch,
@@ -164,6 +201,33 @@ int emu_columns_refusals(void) {
         for (int log_m = 1; log_m <= 14; log_m++)
             pass_dispatch<FieldGL, true>(contig != 0, log_m, e, [&](auto tag) { mat_named |= decltype(tag)::Cfg::MAT; });
     if (mat_named) got |= 128;
+    return got;
+}
+
+// the size limit from both sides (launch.h: fill_pass_args, MAT_MAX_LOG_WORDS), asked on the first pass of a 2^20-row matrix.  bit 0:
+// N * pitch == 2^28 words (pitch 256) is accepted; bit 1: pitch 257 is refused; bit 2: logn + w == 28 (129 columns: w = 8) is accepted;
+// bit 3: logn + w == 29 (257 columns in a pitch of 512) is refused.  15 = as it should be
+int emu_columns_limit(void) {
+    using Twin = ColMatCfg<FieldGL, 7, false>;
+    PassArgs<Twin> at;
+    auto accepted = [&](int w, uint32_t width, uint32_t pitch) {
+        ErasedArgs e;
+        memset(&e, 0, sizeof(e));
+        e.field = field_params(8, GOLDILOCKS);
+        e.n = 20 + w;
+        e.s0 = w;
+        e.batch = 1;
+        e.target_wgs = 16384;
+        e.mat_w = w;
+        e.mat_pitch = pitch;
+        e.mat_width = width;
+        return fill_pass_args<Twin>(e, pass_geometry_of<Twin>(e), at);
+    };
+    int got = 0;
+    if (accepted(4, 2, 256)) got |= 1;
+    if (!accepted(4, 2, 257)) got |= 2;
+    if (accepted(8, 129, 256)) got |= 4;
+    if (!accepted(9, 257, 512)) got |= 8;
     return got;
 }
 
@@ -286,6 +350,12 @@ int main(int argc, char **argv) {
         // many matrices per workgroup and several groups per workgroup (ppw > 1) with a ragged last group
         for (int mode = 0; mode < 3; mode++) {
             bad += one_case(c, 4, 5, 7, 3 * 16 + 1, mode, mode == 1, 2);
+            cases++;
+        }
+        // three passes (logn 17 = 6 + 6 + 5): the middle one has several hi blocks, a first stage above mat_w and a row stride above 1
+        // at once, and is the only launch that neither reads the caller's input nor holds stage 0
+        for (int mode = 0; mode < 3 && !quick; mode++) {
+            bad += one_case(c, 17, 17, 18, 1, mode, mode != 1, mode == 2 ? 2 : 16384);
             cases++;
         }
     }

@@ -407,6 +407,11 @@ int main(int argc, char **argv) {
             bad += one_case(c, 4, 0, 5, 7, 7, 3 * 16 + 1, 2, rep != 0, 2, c.g);
             cases++;
         }
+        // three passes (logn 17 = 6 + 6 + 5): a plain in-place matrix pass between the fused twin and the other end
+        bad += one_case(c, 17, 1, 17, 17, 18, 1, 1, false, 16384, c.p - 1);
+        bad += one_case(c, 17, 4, 17, 18, 17, 1, 1, false, 2, c.g);
+        bad += one_case(c, 17, 0, 17, 18, 18, 1, 2, true, 16384, c.g);
+        cases += 3;
     }
     printf("%s: %ld cases, %ld bad\n", argv[1], cases, bad);
     if (bad == 0 && cases > 0) printf("%s: %ld cases clean\n", argv[1], cases);

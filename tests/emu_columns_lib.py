@@ -22,8 +22,18 @@ def lib():
         L.emu_columns.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                   C.c_int, C.c_uint32]
         L.emu_column_passes.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+        L.emu_columns_geometry.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                           C.POINTER(C.c_uint32)]
         _lib = L
     return _lib
+
+
+def geometry(word_bytes, p, logn, width, pitch, count, target, k, inverse=False):
+    """what launch.h's mat_dispatch + pass_geometry_of give for pass k of plan_column_passes(logn) of a columns call on this shape"""
+    v = (C.c_uint32 * 8)()
+    rc = lib().emu_columns_geometry(word_bytes, p, logn, width, pitch, count, target, k, int(inverse), v)
+    assert rc == 0, rc
+    return {"grid_x": v[0], "grid_y": v[1], "ppw": v[2], "log_up": v[3], "taper": list(v[4:8])}
 
 
 def column_passes(logn):

@@ -98,22 +98,40 @@ def test_the_launcher_refuses_what_it_should():
     assert E.lib().emu_columns_refusals() == 63
 
 
+def test_the_launcher_takes_the_size_limit_at_equality():
+    """launch.h: fill_pass_args accepts a matrix of exactly 2^28 words and a virtual polynomial of exactly 2^28 words (logn 20: pitch
+    256; 129 columns) and refuses one step beyond either (pitch 257; 257 columns): both sides of the boundary on one shape"""
+    import emu_columns_lib as E
+
+    assert E.lib().emu_columns_limit() == 15
+
+
 def _sweep_cases():
     for logn in (4, 5, 8, 9, 10, 12):
         for width in (1, 3, 16, 17, 33):
             p2 = 1 << (width - 1).bit_length()
             for pitch in (width, width + 1, p2 + 16):
                 for count in (1, 3):
-                    yield logn, width, pitch, count
+                    yield logn, width, pitch, count, (0, 1, 2)
+
+
+def _three_pass_cases():
+    """(logn, width, pitch, count, modes): logn 17 = 6 + 6 + 5 -- the middle pass is the only launch with several hi blocks, a first
+    stage above mat_w and a row stride above 1 at once, and the only one that neither reads the caller's input nor holds stage 0 --
+    and one forward case of logn 18 = 6 + 6 + 6"""
+    for width in (1, 17):
+        for pitch in (width, width + 1):
+            yield 17, width, pitch, 1, (0, 1, 2)
+    yield 18, 1, 1, 1, (0,)
 
 
 @pytest.mark.parametrize("cls", sorted(CLASSES))
 def test_columns_in_the_host_model(oracle, cls):
     """pass.h's PassCfg::MAT kernels stepped on the host (tests/emu/emu_columns.cpp, LDS hazard tracker on) through mat_dispatch /
     pass_geometry_of / fill_pass_args over plan_column_passes: forward, scaled and unscaled inverse x logn {4, 5, 8, 9, 10, 12} x
-    width {1, 3, 16, 17, 33} x pitch {width, width + 1, next power of two + 16} x count {1, 3}, in place and out of place, ppw 1 and
-    > 1; buffers of exactly (count * N - 1) * pitch + width words; every live word is the oracle's transform of its column, every
-    padding word keeps its sentinel (>= p: junk on the input side)"""
+    width {1, 3, 16, 17, 33} x pitch {width, width + 1, next power of two + 16} x count {1, 3}, then the three-pass shapes of
+    _three_pass_cases; in place and out of place, ppw 1 and > 1; buffers of exactly (count * N - 1) * pitch + width words; every live
+    word is the oracle's transform of its column, every padding word keeps its sentinel (>= p: junk on the input side)"""
     import emu_columns_lib as E
 
     L = E.lib()
@@ -123,21 +141,25 @@ def test_columns_in_the_host_model(oracle, cls):
     assert sent >= p
     rng = np.random.default_rng(31)
     tables, case = {}, 0
-    for logn, width, pitch, count in _sweep_cases():
+    for logn, width, pitch, count, modes in list(_sweep_cases()) + list(_three_pass_cases()):
         n = 1 << logn
         if logn not in tables:
             tables[logn] = oracle.make_table(1, n, p, g, wb)
         T = tables[logn]
+        assert len(E.column_passes(logn)) == (3 if logn >= 17 else 2 if logn >= 9 else 1)
         words = (count * n - 1) * pitch + width
         x = (rng.integers(0, 2**63, size=(count, n, width), dtype=np.uint64) % np.uint64(p)).astype(dt)
         x[0, 0, 0], x[-1, -1, -1] = p - 1, 0
         cols = np.ascontiguousarray(x.transpose(0, 2, 1)).reshape(count * width, n)
-        fwd, inv = oracle.ntt(cols, T, p), oracle.intt(cols, T, p)
-        unscaled = oracle.pointwise(inv, np.full_like(inv, n % p), p)
+        fwd = oracle.ntt(cols, T, p)
+        inv = oracle.intt(cols, T, p) if modes != (0,) else None
+        unscaled = oracle.pointwise(inv, np.full_like(inv, n % p), p) if modes != (0,) else None
         live = np.zeros(count * n * pitch, dtype=bool).reshape(count * n, pitch)
         live[:, :width] = True
         live = live.reshape(-1)[:words]
         for mode, want_cols in ((0, fwd), (1, inv), (2, unscaled)):
+            if mode not in modes:
+                continue
             want = np.ascontiguousarray(want_cols.reshape(count, width, n).transpose(0, 2, 1))
             in_place = bool(case & 1)
             target = 2 if case & 2 else 16384
@@ -153,7 +175,7 @@ def test_columns_in_the_host_model(oracle, cls):
             assert np.all(out[~live] == (sent if in_place else sent - 1)), key  # padding of the output keeps its contents
             if not in_place:
                 assert np.array_equal(a, a0), key  # the input is read only
-    assert case == 6 * 5 * 3 * 2 * 3
+    assert case == 6 * 5 * 3 * 2 * 3 + 2 * 2 * 3 + 1
     # 16 matrices per workgroup (logn 4), several groups per workgroup, a ragged last group
     n, width, pitch, count = 16, 5, 7, 3 * 16 + 1
     T = oracle.make_table(1, n, p, g, wb)
@@ -191,3 +213,43 @@ def test_error_contract_without_a_device():
     for name in ("forward_columns", "inverse_columns", "column_passes"):
         assert hasattr(eng.NTTPlan, name)
 
+
+def _library_column_target():
+    """the workgroup count the library sizes its column launches for: the initialiser of target_wgs_col in ntt_api.hip"""
+    src = open(os.path.join(ROOT, "ntt_aie_amd", "csrc", "ntt_api.hip")).read()
+    m = re.search(r"^\s*uint32_t\s+target_wgs_col\s*=\s*([0-9][0-9\s*]*);", src, re.M)
+    assert m, "the initialiser of target_wgs_col was not found in ntt_api.hip"
+    target = 1
+    for f in m.group(1).split("*"):
+        target *= int(f)
+    return target
+
+
+def test_gpu_loop_shapes_do_loop():
+    """tests/test_gpu_columns_large.py's LOOP_SHAPES exist to run the batch loop of the matrix kernels on hardware.  With launch.h's own
+    mat_dispatch / pass_geometry_of (emu_columns_geometry) at the library's own column target, every pass of every such shape, in
+    every word class and direction, streams two groups or more per workgroup (ppw >= 2), is tapered over at least two levels, and its
+    count fills neither the last workgroup (a multiple of 2^log_up; where a workgroup holds several matrices at all) nor the last row
+    of the batch loop (a multiple of ppw << log_up): a change of the target or of the tile shapes cannot quietly take the GPU test
+    back to ppw == 1"""
+    import emu_columns_lib as E
+    from test_gpu_columns_large import LOOP_SHAPES
+
+    target = _library_column_target()
+    assert target >= 2
+    assert len(LOOP_SHAPES) >= 2 and {len(E.column_passes(s[0])) for s in LOOP_SHAPES} >= {1, 2}
+    several_per_workgroup = False
+    for logn, width, pitch, count in LOOP_SHAPES:
+        for cls, (wb, p, g) in dict(CLASSES, kyber=(4, 3329, 3)).items():
+            for k in range(len(E.column_passes(logn))):
+                for inverse in (False, True):
+                    geo = E.geometry(wb, p, logn, width, pitch, count, target, k, inverse)
+                    key = (logn, width, pitch, count, cls, k, inverse, geo)
+                    assert geo["ppw"] >= 2, key
+                    assert sum(1 for r in geo["taper"] if r) >= 2 and sum(geo["taper"]) == geo["grid_y"], key
+                    assert count % (geo["ppw"] << geo["log_up"]) != 0, key
+                    if geo["log_up"] > 0:  # (a matrix of two passes never shares its workgroup: every count is a multiple of 2^0)
+                        assert count % (1 << geo["log_up"]) != 0, key
+                        several_per_workgroup = True
+                    assert geo["grid_y"] <= 65535, key  # one launch: the slicing path is not what these shapes are about
+    assert several_per_workgroup

@@ -123,13 +123,24 @@ def _sweep_cases():
                 yield logn, width, pitches[(k + 1) % 3], pitch, (1, 3)[(logn + width + k) & 1]
 
 
+def _three_pass_cases():
+    """(logn, width, in_pitch, pitch, count, blow-ups): logn 17 = 6 + 6 + 5 -- a plain in-place matrix pass lies between the fused twin
+    and the other end -- with the smallest and the largest blow-up, and logn 18 = 6 + 6 + 6 for the coset inverse alone"""
+    for width in (1, 17):
+        for in_pitch, pitch in ((width + 1, width), (width, width + 1)):
+            yield 17, width, in_pitch, pitch, 1, (1, 4)
+    yield 18, 1, 1, 1, 1, ()
+
+
 @pytest.mark.parametrize("cls", sorted(CLASSES))
 def test_both_twins_in_the_host_model(oracle, cls):
     """pass.h's PassCfg::MLDE / MCINV kernels stepped on the host (tests/emu/emu_lde_columns.cpp, LDS hazard tracker on) through
     mat_twin_dispatch / pass_geometry_of / fill_pass_args over plan_column_passes: logn {4, 5, 8, 9, 12} x width {1, 3, 16, 17, 33} x
     three pitches (input and output pitch differ for the LDE) x count 1 or 3, the blow-up cycling through every legal value and the
-    shift through {1, g, p - 1}; buffers of exactly (count * rows - 1) * pitch + width words; every live word is the oracle's network
-    on the expanded / scaled transposed column, every padding word keeps its sentinel (>= p: junk on the input side)"""
+    shift through {1, g, p - 1}, then the three-pass shapes of _three_pass_cases; buffers of exactly (count * rows - 1) * pitch + width
+    words; every live word is the oracle's network on the expanded / scaled transposed column, every padding word keeps its sentinel
+    (>= p: junk on the input side)"""
+    import emu_columns_lib
     import emu_lde_columns_lib as E
 
     L = E.lib()
@@ -138,7 +149,7 @@ def test_both_twins_in_the_host_model(oracle, cls):
     sent = np.iinfo(dt).max - 10
     assert sent >= p
     rng = np.random.default_rng(41)
-    tables, case = {}, 0
+    tables, case, ldes = {}, 0, 0
 
     def flat_of(x, rows, pitch, width, count):
         words = (count * rows - 1) * pitch + width
@@ -149,31 +160,35 @@ def test_both_twins_in_the_host_model(oracle, cls):
         a[live] = x.reshape(-1)
         return a, live
 
-    for logn, width, in_pitch, pitch, count in _sweep_cases():
+    for logn, width, in_pitch, pitch, count, betas in [c + (None,) for c in _sweep_cases()] + list(_three_pass_cases()):
         m = 1 << logn
         if logn not in tables:
             tables[logn] = oracle.make_table(1, m, p, g, wb)
         T = tables[logn]
+        assert len(emu_columns_lib.column_passes(logn)) == (3 if logn >= 17 else 2 if logn >= 9 else 1)
         shift = (1, g, p - 1)[case % 3]
         target = 2 if case & 2 else 16384
-        beta = 1 + case % min(4, logn - 1)
+        if betas is None:
+            betas = (1 + case % min(4, logn - 1),)
         case += 1
         # ---- lde
-        n = m >> beta
-        x = (rng.integers(0, 2**63, size=(count, n, width), dtype=np.uint64) % np.uint64(p)).astype(dt)
-        x[0, 0, 0], x[-1, -1, -1] = p - 1, 0
-        svec = np.array([pow(shift, _bitrev(i, logn - beta), p) for i in range(n)], dtype=dt)
-        cols = np.zeros((count * width, m), dtype=dt)
-        cols[:, :: 1 << beta] = oracle.pointwise(np.ascontiguousarray(x.transpose(0, 2, 1)).reshape(count * width, n), np.broadcast_to(svec, (count * width, n)).copy(), p)
-        want = np.ascontiguousarray(oracle.ntt(cols, T, p).reshape(count, width, m).transpose(0, 2, 1))
-        a, _ = flat_of(x, n, in_pitch, width, count)
-        a0 = a.copy()
-        out, live = flat_of(np.full((count, m, width), sent - 2, dtype=dt), m, pitch, width, count)
-        out[~live] = sent - 1
-        key = (cls, "lde", logn, beta, width, in_pitch, pitch, count, shift, target)
-        assert L.emu_lde_columns(wb, logn, p, T.ctypes.data, a.ctypes.data, in_pitch, out.ctypes.data, pitch, width, count, beta, shift, target) == 0, key
-        assert np.array_equal(out[live], want.reshape(-1)), key
-        assert np.all(out[~live] == sent - 1) and np.array_equal(a, a0), key
+        for beta in betas:
+            n = m >> beta
+            x = (rng.integers(0, 2**63, size=(count, n, width), dtype=np.uint64) % np.uint64(p)).astype(dt)
+            x[0, 0, 0], x[-1, -1, -1] = p - 1, 0
+            svec = np.array([pow(shift, _bitrev(i, logn - beta), p) for i in range(n)], dtype=dt)
+            cols = np.zeros((count * width, m), dtype=dt)
+            cols[:, :: 1 << beta] = oracle.pointwise(np.ascontiguousarray(x.transpose(0, 2, 1)).reshape(count * width, n), np.broadcast_to(svec, (count * width, n)).copy(), p)
+            want = np.ascontiguousarray(oracle.ntt(cols, T, p).reshape(count, width, m).transpose(0, 2, 1))
+            a, _ = flat_of(x, n, in_pitch, width, count)
+            a0 = a.copy()
+            out, live = flat_of(np.full((count, m, width), sent - 2, dtype=dt), m, pitch, width, count)
+            out[~live] = sent - 1
+            key = (cls, "lde", logn, beta, width, in_pitch, pitch, count, shift, target)
+            assert L.emu_lde_columns(wb, logn, p, T.ctypes.data, a.ctypes.data, in_pitch, out.ctypes.data, pitch, width, count, beta, shift, target) == 0, key
+            assert np.array_equal(out[live], want.reshape(-1)), key
+            assert np.all(out[~live] == sent - 1) and np.array_equal(a, a0), key
+            ldes += 1
         # ---- coset inverse, in place and out of place alternating
         y = (rng.integers(0, 2**63, size=(count, m, width), dtype=np.uint64) % np.uint64(p)).astype(dt)
         y[0, 0, 0], y[-1, -1, -1] = p - 1, 0
@@ -190,7 +205,7 @@ def test_both_twins_in_the_host_model(oracle, cls):
         assert np.all(out[~live] == (sent if in_place else sent - 1)), key
         if not in_place:
             assert np.array_equal(a, a0), key
-    assert case == 5 * 5 * 3
+    assert (case, ldes) == (5 * 5 * 3 + 2 * 2 + 1, 5 * 5 * 3 + 2 * 2 * 2)
 
 
 def test_error_contract_without_a_device():
