@@ -43,7 +43,7 @@ EXPORTS = (
 
 def kernel_source_hash() -> str:
     """16 hex digits over the device-code sources (csrc/*.h, *.inc and the kernel *.hip files; not the host-side C-ABI
-    ntt_api.hip / guard.h): the identity of the kernels a profile was collected on.  bench.py and tools/*_summary.py stamp it into
+    ntt_api.hip / guard.h / sequence.h): the identity of the kernels a profile was collected on.  bench.py and tools/*_summary.py stamp it into
     what they write, and bench.py refuses to quote counter values whose stamp differs from the tree it runs in."""
     import glob
     import hashlib
@@ -51,7 +51,7 @@ def kernel_source_hash() -> str:
     h = hashlib.sha256()
     src = os.path.join(_HERE, "csrc")
     for f in sorted(glob.glob(os.path.join(src, "*.h")) + glob.glob(os.path.join(src, "*.inc")) + glob.glob(os.path.join(src, "*.hip"))):
-        if os.path.basename(f) in ("ntt_api.hip", "guard.h"):  # host side of the C-ABI: no device code
+        if os.path.basename(f) in ("ntt_api.hip", "guard.h", "sequence.h"):  # host side of the C-ABI: no device code
             continue
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

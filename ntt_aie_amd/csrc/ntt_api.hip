@@ -1,5 +1,5 @@
-// ntt_api.hip -- C-ABI of libntt_hip.so (include/ntt_hip.h): plan, pass planner,
-// twiddle preparation and launch sequencing.  Host side of what the reference
+// ntt_api.hip -- C-ABI of libntt_hip.so (include/ntt_hip.h): plan, validation,
+// twiddle preparation and the launchers behind the sequences of sequence.h.  Host side of what the reference
 // does in src/test.cpp:62-190 (buffers, table, launch) minus XRT.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -16,6 +16,7 @@
 #include "guard.h"
 #include "kernels.h"
 #include "plan.h"
+#include "sequence.h"
 
 using namespace ntt::host;
 
@@ -77,25 +78,10 @@ struct RoctxRange {
 
 }  // namespace
 
-struct ntt_plan {
-    int logn = 0;
-    uint64_t p = 0;
-    int word_bytes = 0;
+// what the sequences read of a plan is its ntt::PlanFacts base (sequence.h); the rest is the C-ABI's own
+struct ntt_plan : ntt::PlanFacts {
     int device = 0;
-    ntt::FieldParams field = {};  // arithmetic (launch.h: FieldKind) and its Montgomery constants
-    // device tables, table form
-    void *d_tw_fwd = nullptr;
-    void *d_tw_inv = nullptr;
-    void *d_tw_inv_sc = nullptr;  // 8-byte words (both fields): T^-1[N/2 + i] * N^-1, i < N/2 (stage-0 twiddles of the scaled inverse, pass.h: fold_scale)
     bool has_table = false, has_inv = false;
-    uint64_t scale_tf = 0;     // N^-1 in table form
-    uint64_t ninv_plain = 0;   // N^-1 plain
-    uint32_t target_wgs = 8192;  // workgroups per launch the batch loop of a CONTIG pass is sized for (sweep: profiles/)
-    // ... of a column pass: 16384 (their tile streams 8 polynomials per workgroup at N = 2^16, batch 4096, instead of 16): -4 %
-    uint32_t target_wgs_col = 2 * 8192;
-    int dbg = 0;             // experiment build only (NTT_DEBUG_FLAGS); always 0 in the product
-    int force_variant = -1;  // experiment build only (NTT_PASS_VARIANT=k): every CONTIG pass runs kernel variant k; -1 in the product
-    int only_pass = -1;      // experiment build only (NTT_ONLY_PASS=k): a forward run of passes launches pass k alone (power / clock of one kernel); -1 in the product
     int fused = 0;           // experiment build only (NTT_FUSED=1): N = 2^16 Goldilocks forward through the XCD-local fused launch
     void *d_fused_ctl = nullptr;  // counters of the fused launch (plan-owned; null in the product)
     size_t fused_max_batch = 0;
@@ -105,16 +91,8 @@ struct ntt_plan {
     std::vector<PlanAlt> alts;     // launch-time alternatives, ascending min_batch (plan.h: plan_alternatives)
     std::vector<PassDesc> col_passes;  // ntt_forward_columns / ntt_inverse_columns: every stage as a column pass (plan.h: plan_column_passes)
     int forced_alt = -1;           // ntt_plan_set_policy: -1 = by batch, k >= 0 = always alternative k
-    // ntt_plan_set_coset: low-degree extension onto shift * <w_N> from N >> lde_beta coefficients (0 = not set)
-    int lde_beta = 0;
-    uint64_t lde_shift = 0;
-    void *d_lde_s = nullptr;  // s[i] = shift^bitrev(i), table form, max(N >> lde_beta, 4) words (misc_kernels.hip: gen_coset_kernel)
-    int lde_unfused = 0;      // experiment build only (NTT_LDE_UNFUSED=1): ntt_lde takes the separate expansion kernel at every size; 0 in the product
-    // ntt_plan_set_coset_inverse: interpolation from shift * <w_N> (independent of the setting above)
-    bool cinv_set = false;
+    uint64_t lde_shift = 0;   // ntt_plan_set_coset / ntt_plan_set_coset_inverse: the shifts the vectors were made from
     uint64_t cinv_shift = 0;
-    void *d_cinv_u = nullptr;  // u[i] = shift^-bitrev(i) * N^-1, table form, max(N, 4) words (gen_coset_kernel with shift^-1 and the constant N^-1)
-    int cinv_unfused = 0;      // experiment build only (NTT_COSET_INV_UNFUSED=1): ntt_coset_inverse takes the separate row-scaling kernel at every size; 0 in the product
 };
 
 static_assert(NTT_E_NOMEM == NTT_E_NOMEM_GUARD && NTT_E_INTERNAL == NTT_E_INTERNAL_GUARD, "guard.h codes = include/ntt_hip.h codes");
@@ -124,13 +102,13 @@ namespace {
 // frees what a (possibly half-built) plan owns; the device must be current
 void free_plan(ntt_plan *pl) {
     if (!pl) return;
-    if (pl->d_tw_fwd) (void) hipFree(pl->d_tw_fwd);
-    if (pl->d_tw_inv) (void) hipFree(pl->d_tw_inv);
-    if (pl->d_tw_inv_sc) (void) hipFree(pl->d_tw_inv_sc);
+    if (pl->tw_fwd) (void) hipFree(pl->tw_fwd);
+    if (pl->tw_inv) (void) hipFree(pl->tw_inv);
+    if (pl->tw_inv_sc) (void) hipFree(pl->tw_inv_sc);
     if (pl->d_fused_ctl) (void) hipFree(pl->d_fused_ctl);
     if (pl->d_counter) (void) hipFree(pl->d_counter);
-    if (pl->d_lde_s) (void) hipFree(pl->d_lde_s);
-    if (pl->d_cinv_u) (void) hipFree(pl->d_cinv_u);
+    if (pl->lde_s) (void) hipFree(pl->lde_s);
+    if (pl->cinv_u) (void) hipFree(pl->cinv_u);
     delete pl;
 }
 // ntt_plan_create builds the plan under this holder: an exception (std::bad_alloc from the alternatives' vectors)
@@ -151,71 +129,15 @@ size_t lde_s_words(const ntt_plan *pl, int beta) {
     const size_t n = (size_t) 1 << (pl->logn - beta);
     return n < 4 ? 4 : n;
 }
-// does ntt_lde expand inside the first pass of this plan (every alternative's first pass has >= 5 stages from logn = 5 on)
-bool lde_fused(const ntt_plan *pl) { return pl->lde_beta > 0 && pl->logn >= ntt::LDE_MIN_LOG_M && !pl->lde_unfused; }
-
 // words of the coset-interpolation vector (periodic up to one 16-byte chunk of 4-byte words, like the coset vector)
 size_t cinv_u_words(const ntt_plan *pl) {
     const size_t n = (size_t) 1 << pl->logn;
     return n < 4 ? 4 : n;
 }
-// does the inverse CONTIG pass of this decomposition have a twin with the vector sweep (launch.h: pass_dispatch is the rule)
-bool cinv_pass_fused(const ntt_plan *pl, const std::vector<PassDesc> &passes) {
-    if (pl->cinv_unfused || passes.empty() || !passes[0].contig || passes[0].s0 != 0) return false;
-    ntt::ErasedArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n = pl->logn;
-    a.variant = passes[0].variant;
-#if defined(NTT_EXPERIMENT)
-    if (pl->force_variant >= 0) a.variant = pl->force_variant;  // as base_args: the question is about the kernel that will be launched
-#endif
-    static const char selection_only = 0;  // stands for "a vector is present": nothing is launched, only the selection is asked for
-    a.cinv_u = &selection_only;
-    return ntt::with_field(pl->field, [&](auto f) { return ntt::pass_dispatch<decltype(f), true>(true, passes[0].log_m, a, [](auto) {}); });
-}
-// ntt_plan_info 12: ntt_coset_inverse scales inside its last pass whatever the batch (every alternative, or the pinned one)
-bool cinv_fused(const ntt_plan *pl) {
-    if (!pl->cinv_set) return false;
-    if (pl->forced_alt >= 0) return cinv_pass_fused(pl, pl->alts[(size_t) pl->forced_alt].passes);
-    for (const PlanAlt &alt : pl->alts)
-        if (!cinv_pass_fused(pl, alt.passes)) return false;
-    return true;
-}
-
 // the decomposition the launchers run for this batch
-const std::vector<PassDesc> &passes_for(const ntt_plan *pl, size_t batch) {
-    const int k = pl->forced_alt >= 0 ? pl->forced_alt : select_alternative(pl->alts, batch);
-    return pl->alts[(size_t) k].passes;
-}
-
-#if defined(NTT_PHASE_STAMPS)
-void *g_stamp_buf = nullptr;  // diagnostic build: ntt_stamps_set()
-uint32_t g_stamp_records = 0;
-#endif
-
-ntt::ErasedArgs base_args(const ntt_plan *pl, const PassDesc &pd, const void *in, void *out, size_t batch) {
-    ntt::ErasedArgs a;
-    memset(&a, 0, sizeof(a));
-    a.in = in;
-    a.out = out;
-    a.field = pl->field;
-    a.n = pl->logn;
-    a.s0 = pd.s0;
-    a.batch = (uint32_t) batch;
-    a.target_wgs = pd.contig ? pl->target_wgs : pl->target_wgs_col;
-    a.dbg = pl->dbg;
-    a.variant = pd.variant;
-#if defined(NTT_EXPERIMENT)
-    if (pl->force_variant >= 0 && pd.contig) a.variant = pl->force_variant;  // NTT_PASS_VARIANT=k: A/B of a kernel variant
-#endif
-#if defined(NTT_PHASE_STAMPS)
-    // one region per pass kind, so that the passes of one transform do not overwrite each other's records: the CONTIG pass
-    // takes the first half of the buffer, a column pass the second (tools/phase_stamps.py stamps two-pass transforms)
-    a.stamp_records = g_stamp_records / 2;
-    a.stamps = g_stamp_buf ? (char *) g_stamp_buf + (pd.contig ? 0 : (size_t) a.stamp_records * ntt::STAMP_RECORD * 8) : nullptr;
-#endif
-    return a;
-}
+const std::vector<PassDesc> &passes_for(const ntt_plan *pl, size_t batch) { return ntt::passes_for(pl->alts, pl->forced_alt, batch); }
+// ntt_plan_info 12
+bool cinv_fused(const ntt_plan *pl) { return ntt::cinv_fused(*pl, pl->alts, pl->forced_alt); }
 
 // batch == 0 is a valid no-op whatever the pointers are (an empty torch tensor has a null data_ptr)
 int check_io(const ntt_plan *pl, const void *a, const void *b, size_t batch) {
@@ -233,44 +155,17 @@ int check_layout(const ntt_plan *pl, int layout) {
     return NTT_OK;
 }
 
-// PassArgs::pw_scale of a fused pointwise product * scale (plain): scale * R^2, i.e. the table form of the table form
-uint64_t pw_scale_form(const ntt_plan *pl, uint64_t scale_plain) {
-    return to_table_form(to_table_form(scale_plain % pl->p, pl->p, pl->word_bytes), pl->p, pl->word_bytes);
-}
-
-// One pass launch: the arguments every launch of this plan shares, the table of the direction, the ROCTX range;
-// tweak(a) adds what only this launch has.
-template <class Tweak>
-hipError_t launch_one(const ntt_plan *pl, const PassDesc &pd, bool inverse, const char *what, const void *in, void *out, size_t batch,
-                      int layout, hipStream_t s, Tweak &&tweak) {
-    RoctxRange pass(what, pd.contig, pd.s0, pd.log_m);
-    ntt::ErasedArgs a = base_args(pl, pd, in, out, batch);
-    a.tw = inverse ? pl->d_tw_inv : pl->d_tw_fwd;
-    a.layout = layout;
-    tweak(a);
-    return ntt::launch_pass(inverse, pd.contig, pd.log_m, a, s);
-}
-
-// Passes [lo, hi) of a decomposition in execution order (forward: ascending, inverse: descending): the first one launched
-// reads `in`, the others run in place on `out` (which may alias `in`).  tweak(a, i) sees the arguments of pass i.
-template <class Tweak>
-int run_passes(const ntt_plan *pl, const std::vector<PassDesc> &passes, size_t lo, size_t hi, bool inverse, const char *what,
-               const void *in, void *out, size_t batch, int layout, hipStream_t s, Tweak &&tweak) {
-    const void *src = in;
-    for (size_t k = lo; k < hi; k++) {
-        const size_t i = inverse ? lo + (hi - 1 - k) : k;
-#if defined(NTT_EXPERIMENT)
-        if (!inverse && pl->only_pass >= 0 && (int) i != pl->only_pass) continue;  // timing experiment: outputs meaningless
-#endif
-        const hipError_t e = launch_one(pl, passes[i], inverse, what, src, out, batch, layout, s, [&](ntt::ErasedArgs &a) { tweak(a, i); });
-        if (e != hipSuccess) return (int) e;
-        src = out;
+// One step of a sequence (sequence.h) to its launcher, inside the ROCTX range of that pass
+int launch_step(const char *what, const ntt::Step &st, hipStream_t s) {
+    RoctxRange pass(what, st.contig, st.args.s0 - st.args.mat_w, st.log_m);
+    switch (st.family) {
+        case ntt::STEP_MAT: return (int) ntt::launch_mat_pass(st.inverse, st.log_m, st.args, s);
+        case ntt::STEP_PRODUCT: return (int) ntt::launch_product_mid(st.log_m, st.args, s);
+        default: return (int) ntt::launch_pass(st.inverse, st.contig, st.log_m, st.args, s);
     }
-    return NTT_OK;
 }
 
-// in2 != null: transform in[j] * in2[j] * pw_scale (plain) instead of in[j]; the product is folded into
-// the load of the first pass
+// in2 != null: transform in[j] * in2[j] * pw_scale (plain) instead of in[j] (sequence.h: seq_forward)
 // `forced`: the decomposition to run (a product picks ONE for all of its transforms); null = passes_for(batch)
 int run_forward(ntt_plan *pl, const void *d_in, void *d_out, size_t batch, int layout, hipStream_t s,
                 const void *in2 = nullptr, uint64_t pw_scale_plain = 1, const std::vector<PassDesc> *forced = nullptr) {
@@ -281,40 +176,28 @@ int run_forward(ntt_plan *pl, const void *d_in, void *d_out, size_t batch, int l
         batch <= pl->fused_max_batch) {
         // one persistent XCD-local launch; the ordinary passes below then only run (device-side
         // decision, no host sync) if its check kernel did not certify the result
-        hipError_t e = ntt::launch_fused_gl16(d_in, d_out, pl->d_tw_fwd, batch, pl->d_fused_ctl, s, pl->dbg);
+        hipError_t e = ntt::launch_fused_gl16(d_in, d_out, pl->tw_fwd, batch, pl->d_fused_ctl, s, pl->dbg);
         if (e != hipSuccess) return (int) e;
         skip_if = ntt::fused_gl16_ok_word(pl->d_fused_ctl);
         if (pl->dbg & (16 | 32 | 64)) return NTT_OK;  // timing experiments: fused launch alone
     }
 #endif
-    const std::vector<PassDesc> &passes = forced ? *forced : passes_for(pl, batch);
-    const uint64_t pw_scale = in2 ? pw_scale_form(pl, pw_scale_plain) : 0;
-    return run_passes(pl, passes, 0, passes.size(), false, "fwd pass", d_in, d_out, batch, layout, s, [&](ntt::ErasedArgs &a, size_t i) {
-        a.skip_if = skip_if;
-        if (i == 0 && in2) {  // first pass only (d_out may alias d_in)
-            a.in2 = in2;
-            a.pw_scale = pw_scale;
-        }
-    });
+    return ntt::seq_forward(*pl, forced ? *forced : passes_for(pl, batch), d_in, d_out, batch, layout, in2, pw_scale_plain, skip_if,
+                            [&](const ntt::Step &st) { return launch_step("fwd pass", st, s); });
 }
 
 int run_inverse(ntt_plan *pl, const void *d_in, void *d_out, size_t batch, int layout, int scale,
                 hipStream_t s, const std::vector<PassDesc> *forced = nullptr) {
     RoctxRange whole("ntt_inverse");
-    const std::vector<PassDesc> &passes = forced ? *forced : passes_for(pl, batch);
-    return run_passes(pl, passes, 0, passes.size(), true, "inv pass", d_in, d_out, batch, layout, s, [&](ntt::ErasedArgs &a, size_t i) {
-        a.do_scale = (scale && i == 0) ? 1 : 0;
-        a.scale = pl->scale_tf;
-        // 8-byte words: N^-1 rides on the last executed stage (stage 0 of the CONTIG pass) instead of a sweep over the outputs
-        a.tw_sc = a.do_scale ? pl->d_tw_inv_sc : nullptr;
-    });
+    return ntt::seq_inverse(*pl, forced ? *forced : passes_for(pl, batch), d_in, d_out, batch, layout, scale,
+                            [&](const ntt::Step &st) { return launch_step("inv pass", st, s); });
 }
 
-// ntt_forward_columns / ntt_inverse_columns: count matrices [N][pitch], the first `width` words of a row are live.  Every stage is a
-// column pass over the virtual polynomial of 2^(logn + w) words (pass.h: PassCfg::MAT), w = max(LOG_C, ceil_log2(width)).
-// ntt_lde_columns (COL_LDE) and ntt_coset_inverse_columns (COL_CINV) are the same loop with the coset twin in the pass that holds
-// stage 0 (pass.h: PassCfg::MLDE / MCINV): the LDE reads a compact [N >> beta][in_pitch] source there and is out of place only.
-enum ColKind { COL_PLAIN = 0, COL_LDE = 1, COL_CINV = 2 };
+// the four ntt_*_columns calls: validation here, the passes in sequence.h (seq_columns)
+using ntt::COL_CINV;
+using ntt::COL_LDE;
+using ntt::COL_PLAIN;
+using ntt::ColKind;
 int run_columns(ntt_plan *pl, ColKind kind, const void *d_in, size_t in_pitch, void *d_out, size_t pitch, size_t width, size_t count, bool inverse,
                 int scale, void *stream) {
     if (!pl) return NTT_E_ARG;
@@ -333,8 +216,7 @@ int run_columns(ntt_plan *pl, ColKind kind, const void *d_in, size_t in_pitch, v
     // size rule: N * pitch <= 2^NTT_MAX_LOGN words and logn + w <= NTT_MAX_LOGN -- what a size-2^28 transform obeys; the compact
     // source of the LDE obeys it with its own, smaller, row count
     const int beta = kind == COL_LDE ? pl->lde_beta : 0;
-    int w = ntt::col_log_c(pl->word_bytes);
-    while (((size_t) 1 << w) < width && w < NTT_MAX_LOGN) ++w;
+    const int w = ntt::mat_log_w(pl->word_bytes, width);
     if (pl->logn + w > NTT_MAX_LOGN || pitch > ((size_t) 1 << (NTT_MAX_LOGN - pl->logn)) || count > 0x7FFFFFFFull) return NTT_E_ARG;
     if (in_pitch > ((size_t) 1 << (NTT_MAX_LOGN - pl->logn + beta))) return NTT_E_ARG;
     const size_t N = (size_t) 1 << pl->logn, N_in = N >> beta;
@@ -349,34 +231,9 @@ int run_columns(ntt_plan *pl, ColKind kind, const void *d_in, size_t in_pitch, v
     hipStream_t s = (hipStream_t) stream;
     static const char *const names[3][2] = {{"ntt_forward_columns", "fwd columns pass"}, {"ntt_lde_columns", "lde columns pass"}, {"ntt_coset_inverse_columns", "coset inv columns pass"}};
     RoctxRange whole(kind == COL_PLAIN && inverse ? "ntt_inverse_columns" : names[kind][0]);
-    const std::vector<PassDesc> &passes = pl->col_passes;
-    const void *src = d_in;
-    for (size_t k = 0; k < passes.size(); k++) {
-        const PassDesc &pd = passes[inverse ? passes.size() - 1 - k : k];
-        RoctxRange pass(kind == COL_PLAIN && inverse ? "inv columns pass" : names[kind][1], 0, pd.s0, pd.log_m);
-        ntt::ErasedArgs a = base_args(pl, pd, src, d_out, count);
-        a.n = pl->logn + w;
-        a.s0 = pd.s0 + w;
-        a.mat_w = w;
-        a.mat_pitch = (uint32_t) pitch;
-        a.mat_width = (uint32_t) width;
-        a.tw = inverse ? pl->d_tw_inv : pl->d_tw_fwd;
-        a.layout = NTT_LAYOUT_NATURAL;
-        a.do_scale = (inverse && scale && pd.s0 == 0) ? 1 : 0;  // the sweep of the last executed pass, the one that holds stage 0
-        a.scale = pl->scale_tf;
-        if (kind == COL_LDE && pd.s0 == 0) {  // the first executed pass: compact source in, expanded tile out (`in` is not read)
-            a.in = d_out;
-            a.mat_lde_in = d_in;
-            a.mat_lde_s = pl->d_lde_s;
-            a.mat_lde_beta = beta;
-            a.mat_src_pitch = (uint32_t) in_pitch;
-        }
-        if (kind == COL_CINV && pd.s0 == 0) a.mat_cinv_u = pl->d_cinv_u;  // the last executed pass: N^-1 is inside the vector
-        const hipError_t e = ntt::launch_mat_pass(inverse, pd.log_m, a, s);
-        if (e != hipSuccess) return (int) e;
-        src = d_out;
-    }
-    return NTT_OK;
+    const char *what = kind == COL_PLAIN && inverse ? "inv columns pass" : names[kind][1];
+    return ntt::seq_columns(*pl, pl->col_passes, kind, d_in, in_pitch, d_out, pitch, width, count, inverse, scale,
+                            [&](const ntt::Step &st) { return launch_step(what, st, s); });
 }
 
 // device-to-device, no host copy: over xGMI when the devices differ (hipMemcpyPeer), which is what the
@@ -397,8 +254,8 @@ int ntt_version(void) { return 500; /* 0.5.0 */ }
 // the pass kernels of this process write their phase stamps (pass.h: stamp()).  [records][ntt::STAMP_RECORD] 64-bit slots, one
 // record per wave of a launch; null = stamps go to a dummy record.  Never declared in include/ntt_hip.h.
 int ntt_stamps_set(void *d_buf, size_t records) NTT_GUARD {
-    g_stamp_buf = d_buf;
-    g_stamp_records = (uint32_t) (records > 0xFFFFFFFFull ? 0xFFFFFFFFull : records);
+    ntt::stamp_buffer().buf = d_buf;
+    ntt::stamp_buffer().records = (uint32_t) (records > 0xFFFFFFFFull ? 0xFFFFFFFFull : records);
     return NTT_OK;
 } NTT_GUARD_END
 #endif
@@ -501,9 +358,9 @@ int ntt_plan_create(ntt_plan_t *out, int logn, uint64_t p, int word_bytes, int d
 #endif
     DeviceGuard g(device);
     if (g.err != hipSuccess) return (int) g.err;
-    hipError_t e = hipMalloc(&pl->d_tw_fwd, table_bytes(pl));
-    if (e == hipSuccess) e = hipMalloc(&pl->d_tw_inv, table_bytes(pl));
-    if (e == hipSuccess && sc_table_bytes(pl)) e = hipMalloc(&pl->d_tw_inv_sc, sc_table_bytes(pl));
+    hipError_t e = hipMalloc(&pl->tw_fwd, table_bytes(pl));
+    if (e == hipSuccess) e = hipMalloc(&pl->tw_inv, table_bytes(pl));
+    if (e == hipSuccess && sc_table_bytes(pl)) e = hipMalloc(&pl->tw_inv_sc, sc_table_bytes(pl));
     if (e == hipSuccess) e = hipMalloc(&pl->d_counter, sizeof(*pl->d_counter));
 #if defined(NTT_EXPERIMENT)
     if (e == hipSuccess && pl->fused && logn == 16 && word_bytes == 8) {
@@ -548,12 +405,12 @@ int ntt_plan_set_twiddles(ntt_plan_t pl, const void *host_T) NTT_GUARD {
     }
     DeviceGuard g(pl->device);
     if (g.err != hipSuccess) return (int) g.err;
-    hipError_t e = hipMemcpy(pl->d_tw_fwd, buf_f.data(), buf_f.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(pl->d_tw_inv, buf_i.data(), buf_i.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && pl->d_tw_inv_sc && inv_ok) {
+    hipError_t e = hipMemcpy(pl->tw_fwd, buf_f.data(), buf_f.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(pl->tw_inv, buf_i.data(), buf_i.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && pl->tw_inv_sc && inv_ok) {
         std::vector<uint64_t> sc(N / 2);
         for (size_t i = 0; i < N / 2; i++) sc[i] = to_table_form(mulmod(Ti[N / 2 + i], pl->ninv_plain, p), p, 8);
-        e = hipMemcpy(pl->d_tw_inv_sc, sc.data(), sc.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+        e = hipMemcpy(pl->tw_inv_sc, sc.data(), sc.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) return (int) e;
     pl->has_table = true;
@@ -591,10 +448,10 @@ int ntt_plan_generate_twiddles(ntt_plan_t pl, int kind, uint64_t g) NTT_GUARD {
     const uint64_t one_m = to_table_form(1 % p, p, wb);
     DeviceGuard g_(pl->device);
     if (g_.err != hipSuccess) return (int) g_.err;
-    hipError_t e = ntt::launch_gen_table(pl->field, pl->d_tw_fwd, pl->logn, kind, to_table_form(base, p, wb), one_m, nullptr);
-    if (e == hipSuccess) e = ntt::launch_gen_table(pl->field, pl->d_tw_inv, pl->logn, kind, to_table_form(base_inv, p, wb), one_m, nullptr);
-    if (e == hipSuccess && pl->d_tw_inv_sc)  // 8-byte words: stage-0 twiddles of the scaled inverse, T^-1[N/2 + i] * N^-1
-        e = ntt::launch_scale_table(pl->field, (const uint64_t *) pl->d_tw_inv + N / 2, pl->d_tw_inv_sc, N / 2, pl->scale_tf, nullptr);
+    hipError_t e = ntt::launch_gen_table(pl->field, pl->tw_fwd, pl->logn, kind, to_table_form(base, p, wb), one_m, nullptr);
+    if (e == hipSuccess) e = ntt::launch_gen_table(pl->field, pl->tw_inv, pl->logn, kind, to_table_form(base_inv, p, wb), one_m, nullptr);
+    if (e == hipSuccess && pl->tw_inv_sc)  // 8-byte words: stage-0 twiddles of the scaled inverse, T^-1[N/2 + i] * N^-1
+        e = ntt::launch_scale_table(pl->field, (const uint64_t *) pl->tw_inv + N / 2, pl->tw_inv_sc, N / 2, pl->scale_tf, nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) return (int) e;
     pl->has_table = true;
@@ -608,7 +465,7 @@ int ntt_plan_get_twiddles(ntt_plan_t pl, int inverse, void *host_T) NTT_GUARD {
     if (inverse && !pl->has_inv) return NTT_E_NOTINVERTIBLE;
     DeviceGuard g_(pl->device);
     if (g_.err != hipSuccess) return (int) g_.err;
-    hipError_t e = hipMemcpy(host_T, inverse ? pl->d_tw_inv : pl->d_tw_fwd, table_bytes(pl), hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(host_T, inverse ? pl->tw_inv : pl->tw_fwd, table_bytes(pl), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return (int) e;
     // table (Montgomery) form -> plain residues: x * R^-1
     const size_t N = (size_t) 1 << pl->logn;
@@ -635,7 +492,7 @@ int64_t ntt_plan_info(ntt_plan_t pl, int what) NTT_GUARD {
         case 6: return (int64_t) pl->alts.size();
         case 7: return pl->forced_alt;
         case 9: return pl->lde_beta;
-        case 10: return lde_fused(pl) ? 1 : 0;
+        case 10: return ntt::lde_fused(*pl) ? 1 : 0;
         case 11: return pl->cinv_set ? 1 : 0;
         case 12: return cinv_fused(pl) ? 1 : 0;
         case 13: return (int64_t) pl->col_passes.size();
@@ -704,8 +561,8 @@ int ntt_plan_set_coset(ntt_plan_t pl, int log_blowup, uint64_t shift) NTT_GUARD 
         (void) hipFree(d_s);
         return (int) e;
     }
-    if (pl->d_lde_s) (void) hipFree(pl->d_lde_s);  // a replaced setting (configuration call: nothing is in flight on this plan)
-    pl->d_lde_s = d_s;
+    if (pl->lde_s) (void) hipFree(pl->lde_s);  // a replaced setting (configuration call: nothing is in flight on this plan)
+    pl->lde_s = d_s;
     pl->lde_beta = log_blowup;
     pl->lde_shift = shift;
     return NTT_OK;
@@ -729,8 +586,8 @@ int ntt_plan_set_coset_inverse(ntt_plan_t pl, uint64_t shift) NTT_GUARD {
         (void) hipFree(d_u);
         return (int) e;
     }
-    if (pl->d_cinv_u) (void) hipFree(pl->d_cinv_u);  // a replaced setting (configuration call: nothing is in flight on this plan)
-    pl->d_cinv_u = d_u;
+    if (pl->cinv_u) (void) hipFree(pl->cinv_u);  // a replaced setting (configuration call: nothing is in flight on this plan)
+    pl->cinv_u = d_u;
     pl->cinv_set = true;
     pl->cinv_shift = shift;
     return NTT_OK;
@@ -754,9 +611,9 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
     if (src->has_table) {
         DeviceGuard g(device);
         hipError_t e = g.err;
-        if (e == hipSuccess) e = copy_d2d(pl->d_tw_fwd, device, src->d_tw_fwd, src->device, table_bytes(src));
-        if (e == hipSuccess) e = copy_d2d(pl->d_tw_inv, device, src->d_tw_inv, src->device, table_bytes(src));
-        if (e == hipSuccess) e = copy_d2d(pl->d_tw_inv_sc, device, src->d_tw_inv_sc, src->device, sc_table_bytes(src));
+        if (e == hipSuccess) e = copy_d2d(pl->tw_fwd, device, src->tw_fwd, src->device, table_bytes(src));
+        if (e == hipSuccess) e = copy_d2d(pl->tw_inv, device, src->tw_inv, src->device, table_bytes(src));
+        if (e == hipSuccess) e = copy_d2d(pl->tw_inv_sc, device, src->tw_inv_sc, src->device, sc_table_bytes(src));
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) {
             (void) ntt_plan_destroy(pl);
@@ -770,8 +627,8 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
         const size_t bytes = lde_s_words(src, src->lde_beta) * (size_t) src->word_bytes;
         DeviceGuard g(device);
         hipError_t e = g.err;
-        if (e == hipSuccess) e = hipMalloc(&pl->d_lde_s, bytes);
-        if (e == hipSuccess) e = copy_d2d(pl->d_lde_s, device, src->d_lde_s, src->device, bytes);
+        if (e == hipSuccess) e = hipMalloc(&pl->lde_s, bytes);
+        if (e == hipSuccess) e = copy_d2d(pl->lde_s, device, src->lde_s, src->device, bytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) {
             (void) ntt_plan_destroy(pl);
@@ -785,8 +642,8 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
         const size_t bytes = cinv_u_words(src) * (size_t) src->word_bytes;
         DeviceGuard g(device);
         hipError_t e = g.err;
-        if (e == hipSuccess) e = hipMalloc(&pl->d_cinv_u, bytes);
-        if (e == hipSuccess) e = copy_d2d(pl->d_cinv_u, device, src->d_cinv_u, src->device, bytes);
+        if (e == hipSuccess) e = hipMalloc(&pl->cinv_u, bytes);
+        if (e == hipSuccess) e = copy_d2d(pl->cinv_u, device, src->cinv_u, src->device, bytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) {
             (void) ntt_plan_destroy(pl);
@@ -826,19 +683,13 @@ int ntt_lde(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int out_
     hipStream_t s = (hipStream_t) stream;
     RoctxRange whole("ntt_lde");
     const std::vector<PassDesc> &passes = passes_for(pl, batch);
-    if (!lde_fused(pl)) {
+    if (!ntt::lde_fused(*pl)) {
         // expansion as a launch of its own, then the ordinary transform in place
-        hipError_t e = ntt::launch_lde_expand(pl->field, d_in, pl->d_lde_s, d_out, pl->logn, beta, batch, s);
+        hipError_t e = ntt::launch_lde_expand(pl->field, d_in, pl->lde_s, d_out, pl->logn, beta, batch, s);
         if (e != hipSuccess) return (int) e;
         return run_forward(pl, d_out, d_out, batch, out_layout, s, nullptr, 1, &passes);
     }
-    return run_passes(pl, passes, 0, passes.size(), false, "lde pass", d_out, d_out, batch, out_layout, s, [&](ntt::ErasedArgs &a, size_t i) {
-        if (i == 0) {  // expands while it loads: reads d_in (compact) only, writes d_out
-            a.lde_in = d_in;
-            a.lde_s = pl->d_lde_s;
-            a.lde_beta = beta;
-        }
-    });
+    return ntt::seq_lde(*pl, passes, d_in, d_out, batch, out_layout, [&](const ntt::Step &st) { return launch_step("lde pass", st, s); });
 } NTT_GUARD_END
 
 int ntt_forward_profile(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch, int out_layout,
@@ -866,13 +717,14 @@ int ntt_forward_profile(ntt_plan_t pl, const void *d_in, void *d_out, size_t bat
         }
         ev.push_back(x);
     }
-    const void *src = d_in;
     hipError_t e = hipEventRecord(ev[0], s);
-    for (size_t i = 0; i < np && e == hipSuccess; i++) {
-        e = launch_one(pl, passes[i], false, "fwd pass", src, d_out, batch, out_layout, s, [](ntt::ErasedArgs &) {});
-        if (e == hipSuccess) e = hipEventRecord(ev[i + 1], s);
-        src = d_out;
-    }
+    ntt::PlanFacts every_pass = *pl;  // (experiment build: NTT_ONLY_PASS does not apply here, every pass is timed)
+    every_pass.only_pass = -1;
+    if (e == hipSuccess)
+        e = (hipError_t) ntt::seq_forward(every_pass, passes, d_in, d_out, batch, out_layout, nullptr, 1, nullptr, [&](const ntt::Step &st) {
+            const int rc = launch_step("fwd pass", st, s);
+            return rc ? rc : (int) hipEventRecord(ev[(size_t) st.pass + 1], s);
+        });
     if (e == hipSuccess) e = hipEventSynchronize(ev[np]);
     for (size_t i = 0; i < np && e == hipSuccess; i++) e = hipEventElapsedTime(&ms_per_pass[i], ev[i], ev[i + 1]);
     for (auto &x : ev) (void) hipEventDestroy(x);
@@ -921,16 +773,13 @@ int ntt_coset_inverse(ntt_plan_t pl, const void *d_in, void *d_out, size_t batch
     hipStream_t s = (hipStream_t) stream;
     RoctxRange whole("ntt_coset_inverse");
     const std::vector<PassDesc> &passes = passes_for(pl, batch);
-    if (!cinv_pass_fused(pl, passes)) {
+    if (!ntt::cinv_pass_fused(*pl, passes)) {
         // the unscaled inverse, then the scaling as a launch of its own, in place on the output
         rc = run_inverse(pl, d_in, d_out, batch, in_layout, 0, s, &passes);
         if (rc) return rc;
-        return (int) ntt::launch_row_scale(pl->field, d_out, pl->d_cinv_u, pl->logn, batch, s);
+        return (int) ntt::launch_row_scale(pl->field, d_out, pl->cinv_u, pl->logn, batch, s);
     }
-    // the passes of the unscaled inverse; the last one launched (the CONTIG pass) multiplies by the vector before it stores
-    return run_passes(pl, passes, 0, passes.size(), true, "coset inv pass", d_in, d_out, batch, in_layout, s, [&](ntt::ErasedArgs &a, size_t i) {
-        if (i == 0) a.cinv_u = pl->d_cinv_u;
-    });
+    return ntt::seq_coset_inverse(*pl, passes, d_in, d_out, batch, in_layout, [&](const ntt::Step &st) { return launch_step("coset inv pass", st, s); });
 } NTT_GUARD_END
 
 int ntt_pointwise_mul(ntt_plan_t pl, const void *d_a, const void *d_b, void *d_out, size_t batch,
@@ -960,43 +809,12 @@ int ntt_polymul_negacyclic(ntt_plan_t pl, void *d_a, void *d_b, void *d_out, siz
     // With the Longa-Naehrig psi^-1 table the forward negacyclic NTT is the UNSCALED
     // inverse network and the inverse negacyclic NTT is N^-1 * forward network
     // (SURVEY F6-ii), so  c = Fwd( InvU(a) . InvU(b) . N^-1 ).
-    const size_t operand_bytes = (batch << pl->logn) * (size_t) pl->word_bytes;
-    const bool contiguous = (const char *) d_b == (const char *) d_a + operand_bytes && 2 * batch <= 0x7FFFFFFFull;
     const std::vector<PassDesc> &passes = passes_for(pl, batch);
-    const PassDesc &first = passes.front();
-    // Goldilocks, first (or only) pass of 7..12 stages: the radix-8 product kernel exists for that unit size.  A single-pass
-    // size (2^7 <= N <= 2^12) is then ONE launch for the whole product: read a, read b, write c.
-    // ... 4-byte words: radix-16 product kernel, unit sizes 2^6 .. 2^13 (any odd p: all three butterfly streams).
-    // The product launch is not sliced: beyond blockIdx.y's range (tens of millions of tiny polynomials) take the separate
-    // passes, whose launcher slices the batch.  The check IS the launcher's geometry call (launch.h: product_mid_fits).
-    if (first.contig && ntt::product_mid_used(pl->field, first.log_m) &&
-        ntt::product_mid_fits(pl->field, first.log_m, pl->logn, (uint32_t) batch, pl->target_wgs)) {
-        // The column passes (if any) of both unscaled inverse transforms, then ONE launch that runs
-        // the last inverse pass of a and of b, the pointwise product * N^-1 and the first forward pass on each
-        // 2^log_m-word unit while it is workgroup-resident (3 N words of HBM traffic instead of 7 N), then the
-        // forward column passes.
-        for (size_t i = passes.size(); i-- > 1;)
-            for (int op = 0; op < (contiguous ? 1 : 2); op++) {
-                void *buf = op == 0 ? d_a : d_b;
-                hipError_t e = launch_one(pl, passes[i], true, "product: inv pass", buf, buf, contiguous ? 2 * batch : batch, NTT_LAYOUT_NATURAL, s,
-                                          [](ntt::ErasedArgs &) {});
-                if (e != hipSuccess) return (int) e;
-            }
-        {
-            RoctxRange pass("product: fused middle", 1, 0, first.log_m);
-            ntt::ErasedArgs a = base_args(pl, first, d_a, d_out, batch);
-            a.in2 = d_b;
-            a.tw = pl->d_tw_inv;
-            a.tw2 = pl->d_tw_fwd;
-            a.layout = NTT_LAYOUT_NATURAL;
-            a.pw_scale = pw_scale_form(pl, pl->ninv_plain);
-            hipError_t e = ntt::launch_product_mid(first.log_m, a, s);
-            if (e != hipSuccess) return (int) e;
-        }
-        return run_passes(pl, passes, 1, passes.size(), false, "product: fwd pass", d_out, d_out, batch, NTT_LAYOUT_NATURAL, s,
-                          [](ntt::ErasedArgs &, size_t) {});
-    }
-    if (contiguous) {
+    if (ntt::polymul_fused(*pl, passes, batch))  // inverse column passes, the fused middle, forward column passes (sequence.h)
+        return ntt::seq_polymul_fused(*pl, passes, d_a, d_b, d_out, batch, [&](const ntt::Step &st) {
+            return launch_step(st.family == ntt::STEP_PRODUCT ? "product: fused middle" : st.inverse ? "product: inv pass" : "product: fwd pass", st, s);
+        });
+    if (ntt::operands_contiguous(*pl, d_a, d_b, batch)) {
         // the operands are one [2*batch][N] buffer: both unscaled inverse transforms as ONE launch per pass
         // (the decomposition is the one selected for `batch`, as ntt_plan_select documents -- not for the 2*batch rows of this launch)
         rc = run_inverse(pl, d_a, d_a, 2 * batch, NTT_LAYOUT_NATURAL, 0, s, &passes);
@@ -1043,7 +861,7 @@ int ntt_forward_stages(ntt_plan_t pl, const void *d_in, void *d_out, size_t batc
         if (e != hipSuccess) return (int) e;
     }
     for (int st = 0; st <= stage; st++) {
-        hipError_t e = ntt::launch_stage(pl->field, d_out, pl->d_tw_fwd, pl->logn, st, batch, s);
+        hipError_t e = ntt::launch_stage(pl->field, d_out, pl->tw_fwd, pl->logn, st, batch, s);
         if (e != hipSuccess) return (int) e;
     }
     return NTT_OK;

@@ -1,0 +1,298 @@
+// sequence.h -- which launches an entry point makes, in which order and with which arguments: the third shared layer beside
+// launch.h's kernel selection and argument fill.  Host code only (no hip_runtime.h, included by no kernel translation unit): the C-ABI
+// (ntt_api.hip) hands every Step to a GPU launcher, the host index model (tests/emu) steps the same list on the CPU, so the pass order,
+// the buffer each pass reads and the pass that carries an operand are written once.
+//
+// Contract of every sequence below:
+//   * forward passes run in ascending, inverse passes in descending stage order; the first step emitted reads the caller's input,
+//     every later one runs in place on the output (which may alias the input);
+//   * an operand rides on ONE step: in2 / pw_scale and lde_* on the pass that holds stage 0 of a forward sequence (the first
+//     one emitted), do_scale / tw_sc and cinv_u on the pass that holds stage 0 of an inverse sequence (the last one emitted);
+//   * emit(step) returns 0 to go on; anything else ends the sequence and is returned.  Nothing is allocated, nothing dereferenced.
+#pragma once
+#include <stddef.h>
+#include <string.h>
+
+#include "launch.h"
+
+namespace ntt {
+
+// What a sequence needs to know of a plan (ntt_plan is one; the host model fills one from host tables).
+struct PlanFacts {
+    int logn = 0;
+    uint64_t p = 0;
+    int word_bytes = 0;
+    FieldParams field = {};  // arithmetic (launch.h: FieldKind) and its Montgomery constants
+    // tables, table form
+    void *tw_fwd = nullptr;
+    void *tw_inv = nullptr;
+    void *tw_inv_sc = nullptr;  // 8-byte words (both fields): T^-1[N/2 + i] * N^-1, i < N/2 (stage-0 twiddles of the scaled inverse, pass.h: fold_scale)
+    uint64_t scale_tf = 0;      // N^-1 in table form
+    uint64_t ninv_plain = 0;    // N^-1 plain
+    uint32_t target_wgs = 8192;  // workgroups per launch the batch loop of a CONTIG pass is sized for (sweep: profiles/)
+    // ... of a column pass: 16384 (their tile streams 8 polynomials per workgroup at N = 2^16, batch 4096, instead of 16): -4 %
+    uint32_t target_wgs_col = 2 * 8192;
+    // ntt_plan_set_coset: low-degree extension onto shift * <w_N> from N >> lde_beta coefficients (0 = not set)
+    int lde_beta = 0;
+    void *lde_s = nullptr;  // s[i] = shift^bitrev(i), table form, max(N >> lde_beta, 4) words (misc_kernels.hip: gen_coset_kernel)
+    // ntt_plan_set_coset_inverse: interpolation from shift * <w_N> (independent of the setting above)
+    bool cinv_set = false;
+    void *cinv_u = nullptr;  // u[i] = shift^-bitrev(i) * N^-1, table form, max(N, 4) words (gen_coset_kernel with shift^-1 and the constant N^-1)
+    // experiment build only (-DNTT_EXPERIMENT); the product never changes them
+    int dbg = 0;             // NTT_DEBUG_FLAGS
+    int force_variant = -1;  // NTT_PASS_VARIANT=k: every CONTIG pass runs kernel variant k
+    int only_pass = -1;      // NTT_ONLY_PASS=k: a forward run of passes launches pass k alone (power / clock of one kernel)
+    int lde_unfused = 0;     // NTT_LDE_UNFUSED=1: ntt_lde takes the separate expansion kernel at every size
+    int cinv_unfused = 0;    // NTT_COSET_INV_UNFUSED=1: ntt_coset_inverse takes the separate row-scaling kernel at every size
+};
+
+#if defined(NTT_PHASE_STAMPS)
+// diagnostic build: where the pass kernels of this process write their phase stamps (ntt_stamps_set)
+struct StampBuffer {
+    void *buf = nullptr;
+    uint32_t records = 0;
+};
+inline StampBuffer &stamp_buffer() {
+    static StampBuffer b;
+    return b;
+}
+#endif
+
+// which launcher takes a step: launch_pass / launch_mat_pass / launch_product_mid (kernels.h), or their host twins (tests/emu/emu_exec.h)
+enum StepFamily { STEP_PASS = 0, STEP_MAT = 1, STEP_PRODUCT = 2 };
+struct Step {
+    StepFamily family;
+    bool inverse;  // (false for the product middle, which runs both directions)
+    bool contig;
+    int log_m;
+    int pass;  // index into the decomposition the step belongs to
+    ErasedArgs args;
+};
+
+// ---- the decisions that pick a branch -----------------------------------------------------------------------------------------
+
+// the decomposition the launchers run for this batch
+inline const std::vector<host::PassDesc> &passes_for(const std::vector<host::PlanAlt> &alts, int forced_alt, size_t batch) {
+    const int k = forced_alt >= 0 ? forced_alt : host::select_alternative(alts, batch);
+    return alts[(size_t) k].passes;
+}
+
+// does ntt_lde expand inside the first pass of this plan (every alternative's first pass has >= 5 stages from logn = 5 on)
+inline bool lde_fused(const PlanFacts &pf) { return pf.lde_beta > 0 && pf.logn >= LDE_MIN_LOG_M && !pf.lde_unfused; }
+
+// the kernel variant a pass of this plan runs with
+inline int variant_of(const PlanFacts &pf, const host::PassDesc &pd) {
+#if defined(NTT_EXPERIMENT)
+    if (pf.force_variant >= 0 && pd.contig) return pf.force_variant;  // NTT_PASS_VARIANT=k: A/B of a kernel variant
+#endif
+    (void) pf;
+    return pd.variant;
+}
+
+// does the inverse CONTIG pass of this decomposition have a twin with the vector sweep: launch.h's pass_dispatch asked for its
+// selection alone -- nothing is launched
+inline bool cinv_pass_fused(const PlanFacts &pf, const std::vector<host::PassDesc> &passes) {
+    if (pf.cinv_unfused || passes.empty() || !passes[0].contig || passes[0].s0 != 0) return false;
+    ErasedArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = pf.logn;
+    a.variant = variant_of(pf, passes[0]);
+    static const char selection_only = 0;  // stands for "a vector is present"
+    a.cinv_u = &selection_only;
+    return with_field(pf.field, [&](auto f) { return pass_dispatch<decltype(f), true>(true, passes[0].log_m, a, [](auto) {}); });
+}
+// ntt_plan_info 12: ntt_coset_inverse scales inside its last pass whatever the batch (every alternative, or the pinned one)
+inline bool cinv_fused(const PlanFacts &pf, const std::vector<host::PlanAlt> &alts, int forced_alt) {
+    if (!pf.cinv_set) return false;
+    if (forced_alt >= 0) return cinv_pass_fused(pf, alts[(size_t) forced_alt].passes);
+    for (const host::PlanAlt &alt : alts)
+        if (!cinv_pass_fused(pf, alt.passes)) return false;
+    return true;
+}
+
+// PassArgs::pw_scale of a fused pointwise product * scale (plain): scale * R^2, i.e. the table form of the table form
+inline uint64_t pw_scale_form(const PlanFacts &pf, uint64_t scale_plain) {
+    return host::to_table_form(host::to_table_form(scale_plain % pf.p, pf.p, pf.word_bytes), pf.p, pf.word_bytes);
+}
+
+// Does ntt_polymul_negacyclic take the fused middle pass?  Goldilocks, first (or only) pass of 7..12 stages: the radix-8 product
+// kernel exists for that unit size; 4-byte words: radix-16 product kernel, unit sizes 2^6 .. 2^13 (any odd p).  The product launch
+// is not sliced: beyond blockIdx.y's range (tens of millions of tiny polynomials) the separate passes run, whose launcher slices
+// the batch.  The check IS the launcher's geometry call (launch.h: product_mid_fits).
+inline bool polymul_fused(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, size_t batch) {
+    const host::PassDesc &first = passes.front();
+    return first.contig && product_mid_used(pf.field, first.log_m) && product_mid_fits(pf.field, first.log_m, pf.logn, (uint32_t) batch, pf.target_wgs);
+}
+// are the operands of a product one [2 * batch][N] buffer (then a pass over both is ONE launch)
+inline bool operands_contiguous(const PlanFacts &pf, const void *a, const void *b, size_t batch) {
+    const size_t operand_bytes = (batch << pf.logn) * (size_t) pf.word_bytes;
+    return (const char *) b == (const char *) a + operand_bytes && 2 * batch <= 0x7FFFFFFFull;
+}
+
+// log2 of the virtual row length of a matrix call: the column tile's width at least, then the next power of two >= width
+inline int mat_log_w(int word_bytes, size_t width) {
+    int w = col_log_c(word_bytes);
+    while (((size_t) 1 << w) < width && w < MAT_MAX_LOG_WORDS) ++w;
+    return w;
+}
+
+// ---- the steps ------------------------------------------------------------------------------------------------------------------
+
+// the arguments every launch of a plan shares
+inline ErasedArgs step_args(const PlanFacts &pf, const host::PassDesc &pd, const void *in, void *out, size_t batch) {
+    ErasedArgs a;
+    memset(&a, 0, sizeof(a));
+    a.in = in;
+    a.out = out;
+    a.field = pf.field;
+    a.n = pf.logn;
+    a.s0 = pd.s0;
+    a.batch = (uint32_t) batch;
+    a.target_wgs = pd.contig ? pf.target_wgs : pf.target_wgs_col;
+    a.dbg = pf.dbg;
+    a.variant = variant_of(pf, pd);
+#if defined(NTT_PHASE_STAMPS)
+    // one region per pass kind, so that the passes of one transform do not overwrite each other's records: the CONTIG pass
+    // takes the first half of the buffer, a column pass the second (tools/phase_stamps.py stamps two-pass transforms)
+    a.stamp_records = stamp_buffer().records / 2;
+    a.stamps = stamp_buffer().buf ? (char *) stamp_buffer().buf + (pd.contig ? 0 : (size_t) a.stamp_records * STAMP_RECORD * 8) : nullptr;
+#endif
+    return a;
+}
+// ... and the table of the direction: one ordinary pass
+inline Step pass_step(const PlanFacts &pf, const host::PassDesc &pd, int pass, bool inverse, const void *in, void *out, size_t batch, int layout) {
+    Step st{STEP_PASS, inverse, pd.contig, pd.log_m, pass, step_args(pf, pd, in, out, batch)};
+    st.args.tw = inverse ? pf.tw_inv : pf.tw_fwd;
+    st.args.layout = layout;
+    return st;
+}
+
+// Passes [lo, hi) of a decomposition in execution order; tweak(args, i) adds what only pass i has.
+// (experiment build, NTT_ONLY_PASS=k: a forward run emits pass k alone -- a timing experiment, outputs meaningless)
+template <class Tweak, class Emit>
+int seq_passes(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, size_t lo, size_t hi, bool inverse, const void *in, void *out,
+               size_t batch, int layout, Tweak &&tweak, Emit &&emit) {
+    const void *src = in;
+    for (size_t k = lo; k < hi; k++) {
+        const size_t i = inverse ? lo + (hi - 1 - k) : k;
+#if defined(NTT_EXPERIMENT)
+        if (!inverse && pf.only_pass >= 0 && (int) i != pf.only_pass) continue;
+#endif
+        Step st = pass_step(pf, passes[i], (int) i, inverse, src, out, batch, layout);
+        tweak(st.args, i);
+        if (const int rc = emit(st)) return rc;
+        src = out;
+    }
+    return 0;
+}
+
+// ntt_forward (and ntt_forward_profile).  in2 != null: transform in[j] * in2[j] * pw_scale (plain) instead of in[j], the product
+// folded into the load of the first pass only (out may alias in).  skip_if: experiment build, the fallback behind the fused launch.
+template <class Emit>
+int seq_forward(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, const void *in, void *out, size_t batch, int layout, const void *in2,
+                uint64_t pw_scale_plain, const void *skip_if, Emit &&emit) {
+    const uint64_t pw_scale = in2 ? pw_scale_form(pf, pw_scale_plain) : 0;
+    return seq_passes(pf, passes, 0, passes.size(), false, in, out, batch, layout, [&](ErasedArgs &a, size_t i) {
+        a.skip_if = skip_if;
+        if (i == 0 && in2) {
+            a.in2 = in2;
+            a.pw_scale = pw_scale;
+        }
+    }, emit);
+}
+
+// ntt_inverse.  8-byte words: N^-1 rides on the last executed stage (stage 0 of the CONTIG pass, tw_sc) instead of a sweep over
+// the outputs.
+template <class Emit>
+int seq_inverse(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, const void *in, void *out, size_t batch, int layout, int scale, Emit &&emit) {
+    return seq_passes(pf, passes, 0, passes.size(), true, in, out, batch, layout, [&](ErasedArgs &a, size_t i) {
+        a.do_scale = (scale && i == 0) ? 1 : 0;
+        a.scale = pf.scale_tf;
+        a.tw_sc = a.do_scale ? pf.tw_inv_sc : nullptr;
+    }, emit);
+}
+
+// ntt_lde where lde_fused(): the first pass expands while it loads -- it reads the compact `in` through lde_in only and writes
+// `out`; its ordinary input is `out`, which it does not read.
+template <class Emit>
+int seq_lde(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, const void *in, void *out, size_t batch, int layout, Emit &&emit) {
+    return seq_passes(pf, passes, 0, passes.size(), false, out, out, batch, layout, [&](ErasedArgs &a, size_t i) {
+        if (i == 0) {
+            a.lde_in = in;
+            a.lde_s = pf.lde_s;
+            a.lde_beta = pf.lde_beta;
+        }
+    }, emit);
+}
+
+// ntt_coset_inverse where cinv_pass_fused(): the passes of the unscaled inverse; the last one launched (the CONTIG pass)
+// multiplies by the vector, which contains N^-1, before it stores.
+template <class Emit>
+int seq_coset_inverse(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, const void *in, void *out, size_t batch, int layout, Emit &&emit) {
+    return seq_passes(pf, passes, 0, passes.size(), true, in, out, batch, layout, [&](ErasedArgs &a, size_t i) {
+        if (i == 0) a.cinv_u = pf.cinv_u;
+    }, emit);
+}
+
+// ntt_forward_columns / ntt_inverse_columns: count matrices [N][pitch], the first `width` words of a row are live.  Every stage is a
+// column pass over the virtual polynomial of 2^(logn + w) words (pass.h: PassCfg::MAT), w = mat_log_w(width).
+// ntt_lde_columns (COL_LDE) and ntt_coset_inverse_columns (COL_CINV) are the same loop with the coset twin in the pass that holds
+// stage 0 (pass.h: PassCfg::MLDE / MCINV): the LDE reads a compact [N >> beta][in_pitch] source there and is out of place only.
+enum ColKind { COL_PLAIN = 0, COL_LDE = 1, COL_CINV = 2 };
+template <class Emit>
+int seq_columns(const PlanFacts &pf, const std::vector<host::PassDesc> &col_passes, ColKind kind, const void *in, size_t in_pitch, void *out, size_t pitch,
+                size_t width, size_t count, bool inverse, int scale, Emit &&emit) {
+    const int w = mat_log_w(pf.word_bytes, width);
+    const void *src = in;
+    for (size_t k = 0; k < col_passes.size(); k++) {
+        const size_t i = inverse ? col_passes.size() - 1 - k : k;
+        const host::PassDesc &pd = col_passes[i];
+        Step st{STEP_MAT, inverse, false, pd.log_m, (int) i, step_args(pf, pd, src, out, count)};
+        ErasedArgs &a = st.args;
+        a.n = pf.logn + w;
+        a.s0 = pd.s0 + w;
+        a.mat_w = w;
+        a.mat_pitch = (uint32_t) pitch;
+        a.mat_width = (uint32_t) width;
+        a.tw = inverse ? pf.tw_inv : pf.tw_fwd;
+        a.layout = LAYOUT_NATURAL;
+        a.do_scale = (inverse && scale && pd.s0 == 0) ? 1 : 0;  // the sweep of the last executed pass, the one that holds stage 0
+        a.scale = pf.scale_tf;
+        if (kind == COL_LDE && pd.s0 == 0) {  // the first executed pass: compact source in, expanded tile out (`in` is not read)
+            a.in = out;
+            a.mat_lde_in = in;
+            a.mat_lde_s = pf.lde_s;
+            a.mat_lde_beta = pf.lde_beta;
+            a.mat_src_pitch = (uint32_t) in_pitch;
+        }
+        if (kind == COL_CINV && pd.s0 == 0) a.mat_cinv_u = pf.cinv_u;  // the last executed pass: N^-1 is inside the vector
+        if (const int rc = emit(st)) return rc;
+        src = out;
+    }
+    return 0;
+}
+
+// ntt_polymul_negacyclic where polymul_fused(): the column passes (if any) of both unscaled inverse transforms -- per operand, or
+// once over 2 * batch rows when the operands are contiguous -- then ONE launch that runs the last inverse pass of a and of b, the
+// pointwise product * N^-1 and the first forward pass on each 2^log_m-word unit while it is workgroup-resident (tw = inverse table,
+// tw2 = forward table), then the forward column passes in place on `out`.  A single-pass size is the middle step alone.
+template <class Emit>
+int seq_polymul_fused(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, void *a, void *b, void *out, size_t batch, Emit &&emit) {
+    const bool contiguous = operands_contiguous(pf, a, b, batch);
+    for (size_t i = passes.size(); i-- > 1;)
+        for (int op = 0; op < (contiguous ? 1 : 2); op++) {
+            void *buf = op == 0 ? a : b;
+            if (const int rc = emit(pass_step(pf, passes[i], (int) i, true, buf, buf, contiguous ? 2 * batch : batch, LAYOUT_NATURAL))) return rc;
+        }
+    const host::PassDesc &first = passes.front();
+    Step mid{STEP_PRODUCT, false, true, first.log_m, 0, step_args(pf, first, a, out, batch)};
+    mid.args.in2 = b;
+    mid.args.tw = pf.tw_inv;
+    mid.args.tw2 = pf.tw_fwd;
+    mid.args.layout = LAYOUT_NATURAL;
+    mid.args.pw_scale = pw_scale_form(pf, pf.ninv_plain);
+    if (const int rc = emit(mid)) return rc;
+    return seq_passes(pf, passes, 1, passes.size(), false, out, out, batch, LAYOUT_NATURAL, [](ErasedArgs &, size_t) {}, emit);
+}
+
+}  // namespace ntt

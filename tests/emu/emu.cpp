@@ -5,6 +5,8 @@
 // workgroup phase by phase (the role __syncthreads() plays on the GPU), so the
 // index rules, the LDS exchange pattern, the pass planner and the modular
 // arithmetic can be checked against the oracle on a machine without a GPU.
+// Which passes run, in which order and with which arguments is the library's own
+// sequence (csrc/sequence.h), each step through the launchers' dispatchers (emu_exec.h: run_step).
 // It is not a CPU fallback: nothing in the product loads this library.
 #include "emu_exec.h"
 
@@ -16,72 +18,18 @@ using namespace ntt::host;
 // the instrumented builds run in parallel and finish in about a minute instead of six.
 //   0 Goldilocks forward   1 Goldilocks inverse   2 general 64-bit forward   3 general 64-bit inverse
 //   4 4-byte forward       5 4-byte inverse       6 / 7 / 8 fused product middle: Goldilocks / general 64-bit / 4-byte
+// (emu_exec.h: run_step has the same numbering; no matrix pass runs here)
 #ifndef EMU_PARTS
 #define EMU_PARTS 0x1FF
 #endif
-#define EMU_HAS(bit) (((EMU_PARTS) >> (bit)) & 1)
-enum { EMU_ABSENT = -100 };
+using emu::EMU_ABSENT;
 // non-zero: the LDS hazard tracker stays off (emu_set_tracking; the sanitizer sweep checks memory safety, test_emu.py hazards)
 static int g_no_track = 0;
 
 namespace {
 
-// the kernel the GPU launcher runs for this pass (csrc/launch.h: pass_dispatch), stepped on the host; -1 = no such kernel
-template <class F, bool INV>
-int dispatch(bool contig, int log_m, const ErasedArgs &e) {
-    int rc = -1;
-    pass_dispatch<F, INV>(contig, log_m, e, [&](auto tag) { rc = emu::run_pass_launch<typename decltype(tag)::Cfg>(e, !g_no_track); });
-    return rc;
-}
-template <class F>
-int dispatch_product(int log_m, const ErasedArgs &e) {
-    int rc = -1;
-    product_dispatch<F>(log_m, [&](auto tag) { rc = emu::run_product_launch<typename decltype(tag)::Cfg>(e, !g_no_track); });
-    return rc;
-}
-
-// the pass of one family (see EMU_PARTS)
-int dispatch_family(bool inverse, bool contig, int log_m, const ErasedArgs &e) {
-    (void) contig; (void) log_m;
-    if (e.field.kind == FK_M64) {
-#if EMU_HAS(2)
-        if (!inverse) return dispatch<FieldM64, false>(contig, log_m, e);
-#endif
-#if EMU_HAS(3)
-        if (inverse) return dispatch<FieldM64, true>(contig, log_m, e);
-#endif
-    } else if (e.field.kind == FK_GL) {
-#if EMU_HAS(0)
-        if (!inverse) return dispatch<FieldGL, false>(contig, log_m, e);
-#endif
-#if EMU_HAS(1)
-        if (inverse) return dispatch<FieldGL, true>(contig, log_m, e);
-#endif
-    } else {
-#if EMU_HAS(4)
-        if (!inverse) return dispatch<FieldM32, false>(contig, log_m, e);
-#endif
-#if EMU_HAS(5)
-        if (inverse) return dispatch<FieldM32, true>(contig, log_m, e);
-#endif
-    }
-    return EMU_ABSENT;
-}
-
-// the fused product middle of one family
-int dispatch_product_family(int log_m, const ErasedArgs &e) {
-    (void) log_m;
-#if EMU_HAS(7)
-    if (e.field.kind == FK_M64) return dispatch_product<FieldM64>(log_m, e);
-#endif
-#if EMU_HAS(6)
-    if (e.field.kind == FK_GL) return dispatch_product<FieldGL>(log_m, e);
-#endif
-#if EMU_HAS(8)
-    if (e.field.kind == FK_M32) return dispatch_product<FieldM32>(log_m, e);
-#endif
-    return EMU_ABSENT;
-}
+// every step of a sequence (csrc/sequence.h) goes to the kernel the GPU launcher runs for it, stepped on the host; -1 = no such kernel
+int step(const Step &st) { return emu::run_step<(EMU_PARTS) & 0x1FF>(st, !g_no_track, -1); }
 
 }  // namespace
 
@@ -89,37 +37,16 @@ extern "C" {
 
 void emu_set_tracking(int on) { g_no_track = !on; }
 
-// Forward (inverse = 0) or exact inverse (inverse = 1, scaled by N^-1 when scale != 0)
-// of `batch` polynomials, host buffers, table T in plain form (N words).
-// passes_override: 0 = planner's split; otherwise a list "first,col,col,.." packed
-// 4 bits each from the low nibble (used to exercise every tile shape); bits 60..63 = PassDesc::variant of the CONTIG pass.
+// Forward (inverse = 0) or exact inverse (inverse = 1, scaled by N^-1 when scale != 0) of `batch` polynomials as ntt_forward /
+// ntt_inverse sequence them (seq_forward / seq_inverse), host buffers, table T in plain form (N words).
+// passes_override: 0 = planner's split; otherwise a list "first,col,col,.." packed 4 bits each from the low nibble (used to
+// exercise every tile shape); bits 60..63 = PassDesc::variant of the CONTIG pass.  Either is a decomposition of its own
+// handed to the same sequence.
 int emu_transform(int word_bytes, int logn, uint64_t p, const void *T_plain, const void *in, void *out,
                   uint32_t batch, int inverse, int layout, int scale, uint32_t target_wgs,
                   uint64_t passes_override) {
-    const size_t N = (size_t) 1 << logn;
-    std::vector<uint64_t> T(N), Ti;
-    for (size_t i = 0; i < N; i++)
-        T[i] = word_bytes == 4 ? ((const uint32_t *) T_plain)[i] : ((const uint64_t *) T_plain)[i];
-    if (inverse && !invert_table(T, p, Ti)) return -5;
-    const std::vector<uint64_t> &src = inverse ? Ti : T;
-    std::vector<uint32_t> t32;
-    std::vector<uint64_t> t64;
-    const void *tw;
-    if (word_bytes == 4) {
-        t32.resize(N);
-        for (size_t i = 0; i < N; i++) t32[i] = (uint32_t) to_table_form(src[i], p, 4);
-        tw = t32.data();
-    } else {
-        t64.resize(N);
-        for (size_t i = 0; i < N; i++) t64[i] = to_table_form(src[i], p, 8);
-        tw = t64.data();
-    }
-    std::vector<uint64_t> tsc;  // stage-0 twiddles of the scaled Goldilocks inverse, as ntt_plan_set_twiddles makes them
-    if (inverse && word_bytes == 8) {
-        const uint64_t ninv = powmod(p / 2 + 1, (uint64_t) logn, p);
-        tsc.resize(N / 2);
-        for (size_t i = 0; i < N / 2; i++) tsc[i] = to_table_form(mulmod(Ti[N / 2 + i], ninv, p), p, 8);
-    }
+    const emu::HostPlan pl(word_bytes, logn, p, T_plain, target_wgs, inverse != 0);
+    if (inverse && !pl.invertible) return -5;
     std::vector<PassDesc> passes;
     const int contig_variant = (int) (passes_override >> 60);
     passes_override &= (1ull << 60) - 1;
@@ -127,135 +54,96 @@ int emu_transform(int word_bytes, int logn, uint64_t p, const void *T_plain, con
         passes = plan_passes(logn, word_bytes);
     } else {
         int s0 = 0;
-        bool first = true;
         for (uint64_t v = passes_override; v; v >>= 4) {
-            int m = (int) (v & 15);
-            passes.push_back({first, s0, m});
+            const int m = (int) (v & 15);
+            passes.push_back({passes.empty(), s0, m});
             s0 += m;
-            first = false;
         }
         if (s0 != logn) return -1;
     }
-    ErasedArgs e;
-    memset(&e, 0, sizeof(e));
-    e.field = field_params(word_bytes, p);
-    e.n = logn;
-    e.batch = batch;
-    e.layout = layout;
-    e.target_wgs = target_wgs;
-    e.tw = tw;
-    e.tw_sc = tsc.empty() ? nullptr : tsc.data();
-    e.scale = to_table_form(powmod(p / 2 + 1, (uint64_t) logn, p), p, word_bytes);
-    const void *cur = in;
-    const size_t np = passes.size();
-    for (size_t k = 0; k < np; k++) {
-        const size_t i = inverse ? np - 1 - k : k;
-        e.in = cur;
-        e.out = out;
-        e.s0 = passes[i].s0;
-        e.variant = passes[i].contig ? (contig_variant ? contig_variant : passes[i].variant) : 0;
-        e.do_scale = (inverse && scale && i == 0) ? 1 : 0;
-        const int rc = dispatch_family(inverse != 0, passes[i].contig, passes[i].log_m, e);
-        if (rc) return rc;
-        cur = out;
-    }
-    return 0;
+    if (contig_variant && passes[0].contig) passes[0].variant = contig_variant;
+    if (inverse) return seq_inverse(pl, passes, in, out, batch, layout, scale, step);
+    return seq_forward(pl, passes, in, out, batch, layout, nullptr, 1, nullptr, step);
 }
 
 // forward transform of (in * in2 * scale): the fused-product first pass (polymul's last leg)
 int emu_forward_product(int word_bytes, int logn, uint64_t p, const void *T_plain, const void *in, const void *in2,
                         void *out, uint32_t batch, uint64_t scale, uint32_t target_wgs) {
-    const size_t N = (size_t) 1 << logn;
-    std::vector<uint32_t> t32(N);
-    std::vector<uint64_t> t64(N);
-    for (size_t i = 0; i < N; i++) {
-        const uint64_t t = word_bytes == 4 ? ((const uint32_t *) T_plain)[i] : ((const uint64_t *) T_plain)[i];
-        t32[i] = (uint32_t) to_table_form(t, p, 4 == word_bytes ? 4 : 8);
-        t64[i] = to_table_form(t, p, 8);
-    }
-    ErasedArgs e;
-    memset(&e, 0, sizeof(e));
-    // 8-byte words: this entry point has always driven the Goldilocks family whatever p is (its callers pass that prime only)
-    e.field = word_bytes == 8 ? FieldParams{FK_GL, p, 0, 0} : field_params(word_bytes, p);
-    e.n = logn;
-    e.batch = batch;
-    e.target_wgs = target_wgs;
-    e.tw = word_bytes == 4 ? (const void *) t32.data() : (const void *) t64.data();
-    const std::vector<PassDesc> passes = plan_passes(logn, word_bytes);
-    const void *cur = in;
-    for (size_t i = 0; i < passes.size(); i++) {
-        e.in = cur;
-        e.out = out;
-        e.s0 = passes[i].s0;
-        e.in2 = i == 0 ? in2 : nullptr;
-        e.pw_scale = to_table_form(to_table_form(scale % p, p, word_bytes), p, word_bytes);
-        const int rc = dispatch_family(false, passes[i].contig, passes[i].log_m, e);
-        if (rc) return rc;
-        cur = out;
-    }
-    return 0;
+    const emu::HostPlan pl(word_bytes, logn, p, T_plain, target_wgs, false);
+    return seq_forward(pl, plan_passes(logn, word_bytes), in, out, batch, LAYOUT_NATURAL, in2, scale, nullptr, step);
 }
 
 // The negacyclic product c = Fwd(InvU(a) . InvU(b) . N^-1) the way ntt_polymul_negacyclic runs it when the first pass
-// has a product kernel: inverse column passes of both operands, the fused middle pass (pass.h: run_product_pass; the
-// whole product for a single-pass size), forward column passes.  T_plain is the kind-2 table; a and b are overwritten
-// (scratch), like on the device.
+// has a product kernel (seq_polymul_fused): inverse column passes of both operands, the fused middle pass (pass.h:
+// run_product_pass; the whole product for a single-pass size), forward column passes.  T_plain is the kind-2 table; a and b are
+// overwritten (scratch), like on the device.
 int emu_polymul_fused(int word_bytes, int logn, uint64_t p, const void *T_plain, void *a, void *b, void *out, uint32_t batch,
                       uint32_t target_wgs) {
-    const size_t N = (size_t) 1 << logn;
-    std::vector<uint64_t> T(N), Ti;
-    for (size_t i = 0; i < N; i++) T[i] = word_bytes == 4 ? ((const uint32_t *) T_plain)[i] : ((const uint64_t *) T_plain)[i];
-    if (!invert_table(T, p, Ti)) return -5;
-    std::vector<uint64_t> tf64(N), ti64(N);
-    std::vector<uint32_t> tf32(N), ti32(N);
-    for (size_t i = 0; i < N; i++) {
-        tf64[i] = to_table_form(T[i], p, word_bytes);
-        ti64[i] = to_table_form(Ti[i], p, word_bytes);
-        tf32[i] = (uint32_t) tf64[i];
-        ti32[i] = (uint32_t) ti64[i];
-    }
-    const void *tf = word_bytes == 4 ? (const void *) tf32.data() : (const void *) tf64.data();
-    const void *ti = word_bytes == 4 ? (const void *) ti32.data() : (const void *) ti64.data();
+    const emu::HostPlan pl(word_bytes, logn, p, T_plain, target_wgs, true);
+    if (!pl.invertible) return -5;
     const std::vector<PassDesc> passes = plan_passes(logn, word_bytes);
-    const int m0 = passes[0].log_m;
-    ErasedArgs e;
-    memset(&e, 0, sizeof(e));
-    e.field = field_params(word_bytes, p);
-    // unit sizes the product kernels exist for (launch.h: product_dispatch), asked before a and b are touched
-    if (!with_field(e.field, [&](auto f) { return product_dispatch<decltype(f)>(m0, [](auto) {}); })) return -1;
-    e.n = logn;
-    e.batch = batch;
-    e.target_wgs = target_wgs;
-    for (size_t i = passes.size(); i-- > 1;)
-        for (void *buf : {a, b}) {
-            e.in = buf;
-            e.out = buf;
-            e.tw = ti;
-            e.s0 = passes[i].s0;
-            const int rc = dispatch_family(true, passes[i].contig, passes[i].log_m, e);
-            if (rc) return rc;
-        }
-    const uint64_t ninv = powmod(p / 2 + 1, (uint64_t) logn, p);
-    e.in = a;
-    e.in2 = b;
-    e.out = out;
-    e.tw = ti;
-    e.tw2 = tf;
-    e.s0 = 0;
-    e.pw_scale = to_table_form(to_table_form(ninv, p, word_bytes), p, word_bytes);
-    int rc = dispatch_product_family(m0, e);
-    e.in2 = nullptr;
-    e.pw_scale = 0;
-    if (rc) return rc;
-    for (size_t i = 1; i < passes.size(); i++) {
-        e.in = out;
-        e.out = out;
-        e.tw = tf;
-        e.s0 = passes[i].s0;
-        rc = dispatch_family(false, passes[i].contig, passes[i].log_m, e);
-        if (rc) return rc;
-    }
-    return 0;
+    // unit sizes the product kernels exist for (launch.h: product_dispatch; one more than the library takes, launch.h:
+    // product_mid_used), asked before a and b are touched
+    if (!with_field(pl.field, [&](auto f) { return product_dispatch<decltype(f)>(passes[0].log_m, [](auto) {}); })) return -1;
+    return seq_polymul_fused(pl, passes, a, b, out, batch, step);
+}
+
+// The launch list of one call, for tests/test_sequence_cpu.py: nothing runs, no pointer is followed.  call: 0 ntt_forward, 1 ntt_inverse,
+// 2 ntt_lde, 3 ntt_coset_inverse, 4 ntt_forward_columns, 5 ntt_inverse_columns, 6 ntt_lde_columns, 7 ntt_coset_inverse_columns,
+// 8 / 9 ntt_polymul_negacyclic with separate / contiguous operands.  alt: plan alternative, -1 = by batch.  Per step 16 ints: family,
+// inverse, contig, log_m, n, s0, variant, do_scale, batch, then what each pointer IS -- in, out, tw, tw2, tw_sc, in2 (0 null, 1 the
+// caller's input / operand a, 2 the output, 3 operand b, 4 forward table, 5 inverse table, 6 scaled stage-0 table, 7 coset vector,
+// 8 interpolation vector, -1 anything else) -- and a mask of the coset operands: 1 lde_in = input, 2 lde_s = coset vector (then bits
+// 8.. hold lde_beta), 4 cinv_u, 16 / 32 / 64 the same for mat_lde_in, mat_lde_s (bits 8..: mat_lde_beta), mat_cinv_u.  Returns the
+// number of steps, or -1 when they do not fit `cap`.
+int emu_sequence(int call, int word_bytes, int logn, uint64_t p, uint32_t batch, int alt, int scale, int beta, uint32_t width, int *steps, int cap) {
+    const size_t operand_bytes = ((size_t) batch << logn) * (size_t) word_bytes;
+    void *ptr[9];  // tokens, far apart; never followed
+    for (uintptr_t k = 0; k < 9; k++) ptr[k] = (void *) (k << 44);
+    if (call == 9) ptr[3] = (void *) ((uintptr_t) ptr[1] + operand_bytes);
+    PlanFacts pl;
+    pl.logn = logn;
+    pl.p = p;
+    pl.word_bytes = word_bytes;
+    pl.field = field_params(word_bytes, p);
+    pl.tw_fwd = ptr[4];
+    pl.tw_inv = ptr[5];
+    pl.tw_inv_sc = word_bytes == 8 ? ptr[6] : nullptr;
+    pl.lde_s = ptr[7];
+    pl.lde_beta = beta;
+    pl.cinv_u = ptr[8];
+    pl.cinv_set = true;
+    const std::vector<PlanAlt> alts = plan_alternatives(logn, word_bytes, p);
+    if (alt >= (int) alts.size()) return -1;
+    const std::vector<PassDesc> &passes = passes_for(alts, alt, batch);
+    const std::vector<PassDesc> cols = plan_column_passes(logn);
+    int count = 0;
+    auto id = [&](const void *x) {
+        for (int k = 0; k < 9; k++)
+            if (x == ptr[k]) return k;
+        return -1;
+    };
+    auto dump = [&](const Step &st) {
+        if (count >= cap) return -1;
+        const ErasedArgs &a = st.args;
+        const int v[16] = {st.family, st.inverse, st.contig, st.log_m, a.n, a.s0, a.variant, a.do_scale, (int) a.batch, id(a.in), id(a.out), id(a.tw), id(a.tw2),
+                           id(a.tw_sc), id(a.in2),
+                           (a.lde_in == ptr[1]) | (a.lde_s == ptr[7]) << 1 | (a.cinv_u == ptr[8]) << 2 | (a.mat_lde_in == ptr[1]) << 4 | (a.mat_lde_s == ptr[7]) << 5 |
+                               (a.mat_cinv_u == ptr[8]) << 6 | (a.lde_beta + a.mat_lde_beta) << 8};
+        memcpy(steps + 16 * count++, v, sizeof(v));
+        return 0;
+    };
+    int rc = -1;
+    if (call == 0) rc = seq_forward(pl, passes, ptr[1], ptr[2], batch, LAYOUT_NATURAL, nullptr, 1, nullptr, dump);
+    if (call == 1) rc = seq_inverse(pl, passes, ptr[1], ptr[2], batch, LAYOUT_NATURAL, scale, dump);
+    if (call == 2 && lde_fused(pl)) rc = seq_lde(pl, passes, ptr[1], ptr[2], batch, LAYOUT_NATURAL, dump);
+    if (call == 3 && cinv_pass_fused(pl, passes)) rc = seq_coset_inverse(pl, passes, ptr[1], ptr[2], batch, LAYOUT_NATURAL, dump);
+    if (call == 4) rc = seq_columns(pl, cols, COL_PLAIN, ptr[1], width, ptr[2], width, width, batch, false, 0, dump);
+    if (call == 5) rc = seq_columns(pl, cols, COL_PLAIN, ptr[1], width, ptr[2], width, width, batch, true, scale, dump);
+    if (call == 6) rc = seq_columns(pl, cols, COL_LDE, ptr[1], width, ptr[2], width, width, batch, false, 0, dump);
+    if (call == 7) rc = seq_columns(pl, cols, COL_CINV, ptr[1], width, ptr[2], width, width, batch, true, 0, dump);
+    if ((call == 8 || call == 9) && polymul_fused(pl, passes, batch)) rc = seq_polymul_fused(pl, passes, ptr[1], ptr[3], ptr[2], batch, dump);
+    return rc ? -1 : count;
 }
 
 // alternative `alt` of plan_alternatives(logn, word_bytes, p): writes up to 8 (contig, s0, log_m) triples, *min_batch;

@@ -3,8 +3,9 @@
 //
 // TEST INFRASTRUCTURE, a sibling of emu_lde.cpp / emu_coset_inverse.cpp: the same pass.h / plan.h / field.h the HIP kernels are built
 // from, under g++, every thread context of a workgroup stepped phase by phase, with the LDS hazard tracker on.  Every pass is the
-// configuration the launcher's own rule names (csrc/launch.h: mat_dispatch) with the launcher's geometry and argument block
-// (pass_geometry_of / fill_pass_args), sequenced over plan.h's plan_column_passes exactly as ntt_api.hip's run_columns does.
+// configuration the launcher's own rule names (csrc/launch.h: mat_twin_dispatch) with the launcher's geometry and argument block
+// (pass_geometry_of / fill_pass_args), and the launches are the library's own sequence (csrc/sequence.h: seq_columns over plan.h's
+// plan_column_passes).
 //   * as a library (tests/emu_columns_lib.py): emu_columns() on the caller's buffers;
 //   * with -DEMU_COLUMNS_MAIN (tests/test_columns_emu_asan.py, built with ASan + UBSan and linked with oracle/ntt_oracle.c): the sweep
 //     word classes x forward / scaled / unscaled inverse x logn x width x pitch x count x in place / out of place on malloc() buffers of
@@ -20,37 +21,6 @@ using namespace ntt::host;
 #ifndef EMU_COLUMNS_FIELDS
 #define EMU_COLUMNS_FIELDS 7
 #endif
-
-namespace {
-
-int ceil_log2(uint64_t x) {
-    int w = 0;
-    while (((uint64_t) 1 << w) < x) ++w;
-    return w;
-}
-
-template <class F>
-int run_columns(ErasedArgs e, int logn, int w, const void *in, bool inverse, int scale, uint64_t scale_tf) {
-    const std::vector<PassDesc> passes = plan_column_passes(logn);
-    if (passes.empty()) return -3;
-    const void *cur = in;
-    for (size_t k = 0; k < passes.size(); k++) {
-        const PassDesc &pd = passes[inverse ? passes.size() - 1 - k : k];
-        e.in = cur;
-        e.n = logn + w;
-        e.s0 = pd.s0 + w;
-        e.do_scale = (inverse && scale && pd.s0 == 0) ? 1 : 0;
-        e.scale = scale_tf;
-        int rc = -2;  // no such kernel
-        if (inverse) mat_dispatch<F, true>(pd.log_m, [&](auto tag) { rc = emu::run_pass_launch<typename decltype(tag)::Cfg>(e, true); });
-        else mat_dispatch<F, false>(pd.log_m, [&](auto tag) { rc = emu::run_pass_launch<typename decltype(tag)::Cfg>(e, true); });
-        if (rc) return rc;
-        cur = e.out;
-    }
-    return 0;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -73,8 +43,7 @@ int emu_columns_geometry(int word_bytes, uint64_t p, int logn, uint32_t width, u
     if (width == 0 || count == 0 || width > pitch) return -1;
     const std::vector<PassDesc> passes = plan_column_passes(logn);
     if (pass < 0 || (size_t) pass >= passes.size()) return -2;
-    const int log_c = col_log_c(word_bytes);
-    const int w = ceil_log2(width) > log_c ? ceil_log2(width) : log_c;
+    const int w = mat_log_w(word_bytes, width);
     ErasedArgs e;
     memset(&e, 0, sizeof(e));
     e.field = field_params(word_bytes, p);
@@ -108,44 +77,13 @@ int emu_columns(int word_bytes, int logn, uint64_t p, const void *T_plain, const
                 uint32_t count, int inverse, int scale, uint32_t target_wgs) {
     if (width == 0 || count == 0) return 0;
     if (width > pitch) return -1;
-    const size_t N = (size_t) 1 << logn;
-    std::vector<uint64_t> T(N), Ti;
-    for (size_t i = 0; i < N; i++) T[i] = word_bytes == 4 ? ((const uint32_t *) T_plain)[i] : ((const uint64_t *) T_plain)[i];
-    if (inverse && !invert_table(T, p, Ti)) return -5;
-    const std::vector<uint64_t> &src = inverse ? Ti : T;
-    void *tw = malloc(N * (size_t) word_bytes);  // exact-size heap buffer: the plan's own N-word table
-    if (!tw) abort();
-    for (size_t i = 0; i < N; i++) {
-        const uint64_t t = to_table_form(src[i], p, word_bytes);
-        if (word_bytes == 4) ((uint32_t *) tw)[i] = (uint32_t) t;
-        else ((uint64_t *) tw)[i] = t;
-    }
-    const int log_c = col_log_c(word_bytes);
-    const int w = ceil_log2(width) > log_c ? ceil_log2(width) : log_c;
-    ErasedArgs e;
-    memset(&e, 0, sizeof(e));
-    e.field = field_params(word_bytes, p);
-    e.out = out;
-    e.tw = tw;
-    e.batch = count;
-    e.layout = LAYOUT_NATURAL;
-    e.target_wgs = target_wgs;
-    e.mat_w = w;
-    e.mat_pitch = pitch;
-    e.mat_width = width;
-    const uint64_t scale_tf = to_table_form(powmod(p / 2 + 1, (uint64_t) logn, p), p, word_bytes);
-    int rc = -100;
-#if EMU_COLUMNS_FIELDS & 1
-    if (e.field.kind == FK_GL) rc = run_columns<FieldGL>(e, logn, w, in, inverse != 0, scale, scale_tf);
-#endif
-#if EMU_COLUMNS_FIELDS & 2
-    if (e.field.kind == FK_M64) rc = run_columns<FieldM64>(e, logn, w, in, inverse != 0, scale, scale_tf);
-#endif
-#if EMU_COLUMNS_FIELDS & 4
-    if (e.field.kind == FK_M32) rc = run_columns<FieldM32>(e, logn, w, in, inverse != 0, scale, scale_tf);
-#endif
-    free(tw);
-    return rc;
+    const emu::HostPlan pl(word_bytes, logn, p, T_plain, target_wgs, inverse != 0);
+    if (inverse && !pl.invertible) return -5;
+    const std::vector<PassDesc> passes = plan_column_passes(logn);
+    if (passes.empty()) return -3;
+    return seq_columns(pl, passes, COL_PLAIN, in, pitch, out, pitch, width, count, inverse != 0, scale, [](const Step &st) {
+        return emu::run_step<emu::field_parts(EMU_COLUMNS_FIELDS, emu::PARTS_MAT, 3)>(st, true, -2);
+    });
 }
 
 // the launcher's refusals (launch.h: fill_pass_args), asked on one shape.  bit 0: a MAT twin without its three arguments; bit 1: the
@@ -234,29 +172,11 @@ int emu_columns_limit(void) {
 }  // extern "C"
 
 #if defined(EMU_COLUMNS_MAIN)
-#include "../../oracle/ntt_oracle.h"
+#include "emu_sweep.h"
 
 namespace {
 
-uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-uint64_t rnd() {
-    rng_state ^= rng_state << 13;
-    rng_state ^= rng_state >> 7;
-    rng_state ^= rng_state << 17;
-    return rng_state;
-}
-
-struct Class {
-    const char *name;
-    int wb;
-    uint64_t p, g;
-};
-
-uint64_t get(const void *b, int wb, size_t i) { return wb == 4 ? ((const uint32_t *) b)[i] : ((const uint64_t *) b)[i]; }
-void put(void *b, int wb, size_t i, uint64_t v) {
-    if (wb == 4) ((uint32_t *) b)[i] = (uint32_t) v;
-    else ((uint64_t *) b)[i] = v;
-}
+using namespace sweep;
 
 // one case on exact-size buffers; mode 0 forward, 1 scaled inverse, 2 unscaled inverse; returns 0 when every live word equals the
 // oracle's and every padding word is untouched
@@ -264,11 +184,10 @@ int one_case(const Class &c, int logn, uint32_t width, uint32_t pitch, uint32_t 
     const size_t N = (size_t) 1 << logn, wb = (size_t) c.wb;
     const size_t words = ((size_t) count * N - 1) * pitch + width, bytes = words * wb;
     const uint64_t sentinel = c.wb == 4 ? 0xFFFFFFF5ull : 0xFFFFFFFFFFFFFFF5ull;  // >= p for every class
-    std::vector<uint64_t> T64(N);
-    if (oracle_make_table_u64(1, N, T64.data(), c.p, c.g) != 0) return 0;  // 2^logn does not divide p - 1: no such case
-    void *T = malloc(N * wb), *in = malloc(bytes), *out = in_place ? in : malloc(bytes), *cols = malloc((size_t) count * width * N * wb);
-    if (!T || !in || !out || !cols) abort();
-    for (size_t i = 0; i < N; i++) put(T, c.wb, i, T64[i]);
+    void *T = oracle_table(c, N);
+    if (!T) return 0;  // 2^logn does not divide p - 1: no such case
+    void *in = malloc(bytes), *out = in_place ? in : malloc(bytes), *cols = malloc((size_t) count * width * N * wb);
+    if (!in || !out || !cols) abort();
     for (size_t i = 0; i < words; i++) {
         put(in, c.wb, i, sentinel ^ (i & 3));  // padding: non-canonical junk
         if (!in_place) put(out, c.wb, i, sentinel);
@@ -277,17 +196,12 @@ int one_case(const Class &c, int logn, uint32_t width, uint32_t pitch, uint32_t 
     for (size_t m = 0; m < count; m++)
         for (size_t r = 0; r < N; r++)
             for (size_t k = 0; k < width; k++) {
-                const uint64_t rr = rnd();
-                const uint64_t x = (rr & 15) == 0 ? 0 : (rr & 15) == 1 ? c.p - 1 : (rr >> 4) % c.p;
+                const uint64_t x = rnd_residue(c.p);
                 put(in, c.wb, (m * N + r) * pitch + k, x);
                 put(cols, c.wb, (m * width + k) * N + r, x);
             }
-    int orc = 0;
     const size_t nb = (size_t) count * width;
-    if (mode == 0 && c.wb == 4) oracle_ntt_batch_u32((uint32_t *) cols, (uint32_t) N, nb, (const uint32_t *) T, (uint32_t) c.p, 1);
-    else if (mode == 0) oracle_ntt_batch_u64((uint64_t *) cols, N, nb, (const uint64_t *) T, c.p, 1);
-    else orc = c.wb == 4 ? oracle_intt_batch_u32((uint32_t *) cols, (uint32_t) N, nb, (const uint32_t *) T, (uint32_t) c.p, 1)
-                         : oracle_intt_batch_u64((uint64_t *) cols, N, nb, (const uint64_t *) T, c.p, 1);
+    const int orc = oracle_transform(c, cols, N, nb, T, mode != 0);
     if (mode == 2)  // the oracle's inverse is the scaled one: the unscaled words are N times it
         for (size_t i = 0; i < nb * N; i++) put(cols, c.wb, i, mulmod(get(cols, c.wb, i), (uint64_t) N % c.p, c.p));
     const int rc = emu_columns(c.wb, logn, c.p, T, in, out, width, pitch, count, mode != 0, mode == 1, target_wgs);
@@ -312,11 +226,6 @@ int one_case(const Class &c, int logn, uint32_t width, uint32_t pitch, uint32_t 
 
 // usage: emu_columns_sweep <class: gl | m64 | m32> [quick]
 int main(int argc, char **argv) {
-    const Class classes[] = {
-        {"gl", 8, GOLDILOCKS, 7},
-        {"m64", 8, 0xFFFFFFFC00000001ull, 10},  // general 64-bit class: an NTT prime above 2^63 (sums wrap: the carry paths)
-        {"m32", 4, 998244353ull, 3},
-    };
     if (argc < 2) return 2;
     const bool quick = argc > 2;
     long cases = 0, bad = 0;
@@ -324,8 +233,8 @@ int main(int argc, char **argv) {
         fprintf(stderr, "refusals: %d\n", emu_columns_refusals());
         bad++;
     }
-    for (const Class &c : classes) {
-        if (strcmp(c.name, argv[1]) != 0) continue;
+    if (const Class *cp = find_class(argv[1])) {
+        const Class &c = *cp;
         const int logns[] = {4, 5, 8, 9, 10, 12};
         const uint32_t widths[] = {1, 3, 16, 17, 33};
         for (int logn : logns) {
@@ -359,8 +268,6 @@ int main(int argc, char **argv) {
             cases++;
         }
     }
-    printf("%s: %ld cases, %ld bad\n", argv[1], cases, bad);
-    if (bad == 0 && cases > 0) printf("%s: %ld cases clean\n", argv[1], cases);
-    return bad ? 1 : (cases ? 0 : 3);
+    return report(argv[1], cases, bad);
 }
 #endif

@@ -2,8 +2,9 @@
 //
 // TEST INFRASTRUCTURE, a sibling of emu_lde.cpp: the same pass.h / plan.h / field.h the HIP kernels are built from, under g++, every
 // thread context of a workgroup stepped phase by phase, with the LDS hazard tracker on.  Every pass is the configuration the
-// launcher's own rule names (csrc/launch.h: pass_dispatch) with the launcher's argument block (fill_pass_args): the column passes
-// of the unscaled inverse, then the CONTIG pass with the vector operand, exactly as ntt_coset_inverse sequences them.
+// launcher's own rule names (csrc/launch.h: pass_dispatch) with the launcher's argument block (fill_pass_args), and the launches are
+// the library's own sequence (csrc/sequence.h: seq_coset_inverse): the column passes of the unscaled inverse, then the CONTIG pass
+// with the vector operand.
 //   * as a library (tests/emu_coset_inverse_lib.py): emu_coset_inverse() on the caller's buffers;
 //   * with -DEMU_CINV_MAIN (tests/test_coset_inverse_emu_asan.py, built with ASan + UBSan and linked with oracle/ntt_oracle.c): a
 //     sweep over word classes x every fused logM x ragged batches x both layouts x every plan alternative on malloc() buffers of
@@ -20,97 +21,36 @@ using namespace ntt::host;
 #define EMU_CINV_FIELDS 7
 #endif
 
-namespace {
-
-// the passes of one plan alternative in the inverse's execution order (descending): the first one launched reads `in`, the others
-// run in place on e.out; pass 0 (CONTIG, launched last) carries the vector
-template <class F>
-int run_cinv(ErasedArgs e, const void *in, const void *u, const std::vector<PassDesc> &passes) {
-    if (passes.empty() || !passes[0].contig || passes[0].s0 != 0) return -1;
-    const void *cur = in;
-    for (size_t k = passes.size(); k-- > 0;) {
-        const PassDesc &pd = passes[k];
-        e.s0 = pd.s0;
-        e.in = cur;
-        e.variant = pd.contig ? pd.variant : 0;
-        e.cinv_u = k == 0 ? u : nullptr;
-        int rc = k == 0 ? -2 : -3;  // no such kernel
-        pass_dispatch<F, true>(pd.contig, pd.log_m, e, [&](auto tag) { rc = emu::run_pass_launch<typename decltype(tag)::Cfg>(e, true); });
-        if (rc) return rc;
-        cur = e.out;
-    }
-    return 0;
-}
-
-}  // namespace
-
 extern "C" {
 
 // number of launch-time alternatives of the size-2^logn plan (plan.h: plan_alternatives)
 int emu_cinv_alternatives(int word_bytes, int logn, uint64_t p) { return (int) plan_alternatives(logn, word_bytes, p).size(); }
 
-// does the CONTIG pass of alternative `alt` have a twin with the vector sweep: the launcher's rule, asked without running anything
+// does the CONTIG pass of alternative `alt` have a twin with the vector sweep: the library's own question (sequence.h: cinv_pass_fused)
 int emu_cinv_fused(int word_bytes, int logn, uint64_t p, int alt) {
     const std::vector<PlanAlt> alts = plan_alternatives(logn, word_bytes, p);
     if (alt < 0 || alt >= (int) alts.size()) return -1;
-    const PassDesc &pd = alts[(size_t) alt].passes[0];
-    ErasedArgs e;
-    memset(&e, 0, sizeof(e));
-    e.n = logn;
-    e.variant = pd.variant;
-    e.cinv_u = &e;  // non-null: only the selection is asked for
-    return with_field(field_params(word_bytes, p), [&](auto f) { return pass_dispatch<decltype(f), true>(true, pd.log_m, e, [](auto) {}); }) ? 1 : 0;
+    PlanFacts pl;
+    pl.logn = logn;
+    pl.field = field_params(word_bytes, p);
+    return cinv_pass_fused(pl, alts[(size_t) alt].passes) ? 1 : 0;
 }
 
 // One coset interpolation as ntt_coset_inverse runs it where it is fused.  T_plain: the size-2^logn table, plain residues; in, out:
 // [batch][2^logn] words (out may be in); alt: plan alternative, -1 = by batch.
+// -2 / -3: no kernel for the last / an earlier pass (or the launcher refuses its arguments: -2), -4: no such alternative
 int emu_coset_inverse(int word_bytes, int logn, uint64_t p, const void *T_plain, uint64_t shift, const void *in, void *out, uint32_t batch,
                       int layout, uint32_t target_wgs, int alt) {
     if (shift == 0 || shift >= p) return -1;
-    const uint64_t shift_inv = invmod(shift, p);
-    if (shift_inv == 0) return -5;
-    const size_t M = (size_t) 1 << logn;
-    std::vector<uint64_t> T(M), Ti;
-    for (size_t i = 0; i < M; i++) T[i] = word_bytes == 4 ? ((const uint32_t *) T_plain)[i] : ((const uint64_t *) T_plain)[i];
-    if (!invert_table(T, p, Ti)) return -5;
-    // exact-size heap buffers: the inverse table and the vector of ntt_plan_set_coset_inverse, u[i] = shift^-bitrev(i) * M^-1, M words
-    void *tw = malloc(M * (size_t) word_bytes), *u = malloc(M * (size_t) word_bytes);
-    if (!tw || !u) abort();
-    const uint64_t minv = powmod(p / 2 + 1, (uint64_t) logn, p);
-    for (size_t i = 0; i < M; i++) {
-        const uint64_t t = to_table_form(Ti[i], p, word_bytes);
-        const uint64_t v = to_table_form(mulmod(powmod(shift_inv, bitrev(i, logn), p), minv, p), p, word_bytes);
-        if (word_bytes == 4) ((uint32_t *) tw)[i] = (uint32_t) t, ((uint32_t *) u)[i] = (uint32_t) v;
-        else ((uint64_t *) tw)[i] = t, ((uint64_t *) u)[i] = v;
-    }
+    emu::HostPlan pl(word_bytes, logn, p, T_plain, target_wgs, true);
+    if (!pl.invertible || !pl.set_coset_inverse(shift)) return -5;
     const std::vector<PlanAlt> alts = plan_alternatives(logn, word_bytes, p);
-    const int k = alt >= 0 ? alt : select_alternative(alts, batch);
-    int rc = -4;
-    if (k < (int) alts.size()) {
-        ErasedArgs e;
-        memset(&e, 0, sizeof(e));
-        e.field = field_params(word_bytes, p);
-        e.out = out;
-        e.tw = tw;
-        e.n = logn;
-        e.batch = batch;
-        e.layout = layout;
-        e.target_wgs = target_wgs;
-        const std::vector<PassDesc> &passes = alts[(size_t) k].passes;
-        rc = -100;
-#if EMU_CINV_FIELDS & 1
-        if (e.field.kind == FK_GL) rc = run_cinv<FieldGL>(e, in, u, passes);
-#endif
-#if EMU_CINV_FIELDS & 2
-        if (e.field.kind == FK_M64) rc = run_cinv<FieldM64>(e, in, u, passes);
-#endif
-#if EMU_CINV_FIELDS & 4
-        if (e.field.kind == FK_M32) rc = run_cinv<FieldM32>(e, in, u, passes);
-#endif
-    }
-    free(tw);
-    free(u);
-    return rc;
+    if (alt >= (int) alts.size()) return -4;
+    const std::vector<PassDesc> &passes = passes_for(alts, alt, batch);
+    if (!passes[0].contig || passes[0].s0 != 0) return -1;
+    return seq_coset_inverse(pl, passes, in, out, batch, layout, [](const Step &st) {
+        return emu::run_step<emu::field_parts(EMU_CINV_FIELDS, emu::PARTS_PASS, 2)>(st, true, st.args.s0 == 0 ? -2 : -3);
+    });
 }
 
 // the launcher's refusals (launch.h: fill_pass_args), asked on one shape: bit 0 a twin without its vector, bit 1 the vector on the
@@ -141,63 +81,33 @@ int emu_cinv_refusals(void) {
 }  // extern "C"
 
 #if defined(EMU_CINV_MAIN)
-#include "../../oracle/ntt_oracle.h"
+#include "emu_sweep.h"
 
 namespace {
 
-uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-uint64_t rnd() {
-    rng_state ^= rng_state << 13;
-    rng_state ^= rng_state >> 7;
-    rng_state ^= rng_state << 17;
-    return rng_state;
-}
-
-struct Class {
-    const char *name;
-    int wb;
-    uint64_t p, g;
-};
+using namespace sweep;
 
 // one case on exact-size buffers; returns 0 when every word equals the oracle's
 int one_case(const Class &c, int logn, uint32_t batch, int layout, int alt, uint64_t shift, bool in_place, uint32_t target_wgs) {
     const size_t M = (size_t) 1 << logn;
     const size_t wb = (size_t) c.wb, bytes = (size_t) batch * M * wb;
-    std::vector<uint64_t> T64(M);
-    if (oracle_make_table_u64(1, M, T64.data(), c.p, c.g) != 0) return 0;  // 2^logn does not divide p - 1: no such case
-    void *T = malloc(M * wb), *in = malloc(bytes), *out = in_place ? in : malloc(bytes), *want = malloc(bytes);
-    if (!T || !in || !out || !want) abort();
-    for (size_t i = 0; i < M; i++) {
-        if (c.wb == 4) ((uint32_t *) T)[i] = (uint32_t) T64[i];
-        else ((uint64_t *) T)[i] = T64[i];
-    }
+    void *T = oracle_table(c, M);
+    if (!T) return 0;  // 2^logn does not divide p - 1: no such case
+    void *in = malloc(bytes), *out = in_place ? in : malloc(bytes), *want = malloc(bytes);
+    if (!in || !out || !want) abort();
     if (!in_place) memset(out, 0xEE, bytes);
-    for (size_t i = 0; i < (size_t) batch * M; i++) {
-        const uint64_t r = rnd();
-        const uint64_t x = (r & 15) == 0 ? 0 : (r & 15) == 1 ? c.p - 1 : (r >> 4) % c.p;  // 0 and p - 1 among the inputs
-        if (c.wb == 4) ((uint32_t *) want)[i] = (uint32_t) x;
-        else ((uint64_t *) want)[i] = x;
-    }
+    for (size_t i = 0; i < (size_t) batch * M; i++) put(want, c.wb, i, rnd_residue(c.p));
     // the input is the natural-order words in `layout`; the expectation is the oracle's scaled inverse of the natural-order words ...
     for (size_t b = 0; b < batch; b++) {
-        if (layout) {
-            if (c.wb == 4) oracle_block16_u32((uint32_t *) in + b * M, (const uint32_t *) want + b * M, (uint32_t) M);
-            else oracle_block16_u64((uint64_t *) in + b * M, (const uint64_t *) want + b * M, M);
-        } else {
-            memcpy((char *) in + b * M * wb, (const char *) want + b * M * wb, M * wb);
-        }
+        if (layout) oracle_block16(c, (char *) in + b * M * wb, (const char *) want + b * M * wb, M);
+        else memcpy((char *) in + b * M * wb, (const char *) want + b * M * wb, M * wb);
     }
-    int orc;
-    if (c.wb == 4) orc = oracle_intt_batch_u32((uint32_t *) want, (uint32_t) M, batch, (const uint32_t *) T, (uint32_t) c.p, 1);
-    else orc = oracle_intt_batch_u64((uint64_t *) want, M, batch, (const uint64_t *) T, c.p, 1);
+    const int orc = oracle_transform(c, want, M, batch, T, true);
     // ... times shift^-bitrev(i)
     const uint64_t shift_inv = invmod(shift, c.p);
     for (size_t i = 0; i < M; i++) {
         const uint64_t f = powmod(shift_inv, bitrev(i, logn), c.p);
-        for (size_t b = 0; b < batch; b++) {
-            if (c.wb == 4) ((uint32_t *) want)[b * M + i] = (uint32_t) mulmod(((uint32_t *) want)[b * M + i], f, c.p);
-            else ((uint64_t *) want)[b * M + i] = mulmod(((uint64_t *) want)[b * M + i], f, c.p);
-        }
+        for (size_t b = 0; b < batch; b++) put(want, c.wb, b * M + i, mulmod(get(want, c.wb, b * M + i), f, c.p));
     }
     const int rc = emu_coset_inverse(c.wb, logn, c.p, T, shift, in, out, batch, layout, target_wgs, alt);
     const int bad = orc != 0 || rc != 0 || memcmp(out, want, bytes) != 0;
@@ -213,16 +123,11 @@ int one_case(const Class &c, int logn, uint32_t batch, int layout, int alt, uint
 
 // usage: emu_cinv_sweep <class: gl | m64 | m32> [quick]
 int main(int argc, char **argv) {
-    const Class classes[] = {
-        {"gl", 8, GOLDILOCKS, 7},
-        {"m64", 8, 0xFFFFFFFC00000001ull, 10},  // general 64-bit class: an NTT prime above 2^63 (sums wrap: the carry paths)
-        {"m32", 4, 998244353ull, 3},
-    };
     if (argc < 2) return 2;
     const bool quick = argc > 2;
     long cases = 0, bad = 0;
-    for (const Class &c : classes) {
-        if (strcmp(c.name, argv[1]) != 0) continue;
+    if (const Class *cp = find_class(argv[1])) {
+        const Class &c = *cp;
         // every size whose plan has a fused last pass, every alternative (so every CONTIG shape: radix-16 5..12, 13, 14 of 4-byte
         // words, radix-8 7..12 as the first pass of a two-pass plan and as variant 1).  target_wgs alternates between the plan's
         // value (ppw = 1 at these batches) and 2 (a workgroup streams several polynomial groups: ppw > 1, ragged last row)
@@ -252,8 +157,6 @@ int main(int argc, char **argv) {
             cases++;
         }
     }
-    printf("%s: %ld cases, %ld bad\n", argv[1], cases, bad);
-    if (bad == 0 && cases > 0) printf("%s: %ld cases clean\n", argv[1], cases);
-    return bad ? 1 : (cases ? 0 : 3);
+    return report(argv[1], cases, bad);
 }
 #endif

@@ -1,7 +1,8 @@
-// emu_exec.h -- the stepping part of the host index model, shared by emu.cpp and emu_lde.cpp: the LDS hazard tracker, the
-// executors that step every thread context of a workgroup phase by phase (the role __syncthreads() plays on the GPU), and
-// one function that runs a pass -- or the product's fused middle pass -- over its whole grid with the argument block the GPU
-// launcher fills (csrc/launch.h: fill_pass_args / fill_product_args).  TEST INFRASTRUCTURE.
+// emu_exec.h -- the stepping part of the host index model, shared by every emu*.cpp: the LDS hazard tracker, the executors that
+// step every thread context of a workgroup phase by phase (the role __syncthreads() plays on the GPU), one function that runs a
+// pass -- or the product's fused middle pass -- over its whole grid with the argument block the GPU launcher fills (csrc/launch.h:
+// fill_pass_args / fill_product_args), run_step, which hands a step of the library's own launch list (csrc/sequence.h) to it through
+// the launchers' dispatchers, and HostPlan, the plan those lists are made from.  TEST INFRASTRUCTURE.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -11,7 +12,7 @@
 #include <vector>
 
 #define NTT_EMU_TRACK 1
-#include "../../ntt_aie_amd/csrc/launch.h"
+#include "../../ntt_aie_amd/csrc/sequence.h"
 
 namespace emu {
 
@@ -193,5 +194,112 @@ int run_product_launch(const ErasedArgs &e, bool track) {
         }
     return 0;
 }
+
+// ---- one step of a sequence (csrc/sequence.h), as ntt_api.hip's launch_step hands it to the GPU launchers --------------------------
+// PARTS: which template families the translation unit instantiates (bit set = compiled in); a step of an absent one returns EMU_ABSENT.
+//   ordinary passes   0 Goldilocks forward   1 Goldilocks inverse   2 general 64-bit forward   3 general 64-bit inverse
+//                     4 4-byte forward       5 4-byte inverse
+//   product middle    6 Goldilocks           7 general 64-bit       8 4-byte
+//   matrix passes     9 .. 14, in the order of 0 .. 5
+// The per-file masks that name FIELDS (bit 0 Goldilocks, 1 general 64-bit, 2 4-byte words) become parts through field_parts.
+enum { EMU_ABSENT = -100 };
+enum { PARTS_PASS = 0, PARTS_PRODUCT = 6, PARTS_MAT = 9 };
+// the parts of `fields` in the group that starts at bit `base`; dirs: 1 forward, 2 inverse, 3 both
+constexpr unsigned field_parts(unsigned fields, int base, unsigned dirs) {
+    unsigned v = 0;
+    for (int k = 0; k < 3; k++)
+        if ((fields >> k) & 1) v |= dirs << (base + 2 * k);
+    return v;
+}
+
+template <unsigned PARTS, class F, int K>  // K: 0 Goldilocks, 1 general 64-bit, 2 4-byte words
+int run_step_of(const Step &st, bool track, int no_kernel) {
+    const ErasedArgs &e = st.args;
+    int rc = no_kernel;
+    auto pass = [&](auto tag) { rc = run_pass_launch<typename decltype(tag)::Cfg>(e, track); };
+    if (st.family == STEP_PRODUCT) {
+        if constexpr ((PARTS >> (PARTS_PRODUCT + K)) & 1) product_dispatch<F>(st.log_m, [&](auto tag) { rc = run_product_launch<typename decltype(tag)::Cfg>(e, track); });
+        else rc = EMU_ABSENT;
+    } else if (st.family == STEP_MAT) {
+        constexpr unsigned dirs = (PARTS >> (PARTS_MAT + 2 * K)) & 3;
+        rc = (dirs >> (st.inverse ? 1 : 0)) & 1 ? rc : EMU_ABSENT;
+        if constexpr (dirs & 1) if (!st.inverse) mat_twin_dispatch<F, false>(st.log_m, e, pass);
+        if constexpr (dirs & 2) if (st.inverse) mat_twin_dispatch<F, true>(st.log_m, e, pass);
+    } else {
+        constexpr unsigned dirs = (PARTS >> (PARTS_PASS + 2 * K)) & 3;
+        rc = (dirs >> (st.inverse ? 1 : 0)) & 1 ? rc : EMU_ABSENT;
+        if constexpr (dirs & 1) if (!st.inverse) pass_dispatch<F, false>(st.contig, st.log_m, e, pass);
+        if constexpr (dirs & 2) if (st.inverse) pass_dispatch<F, true>(st.contig, st.log_m, e, pass);
+    }
+    return rc;
+}
+// 0; `no_kernel` when the dispatcher names no kernel for the step; -2 when the launcher would refuse its arguments
+template <unsigned PARTS>
+int run_step(const Step &st, bool track, int no_kernel) {
+    if (st.args.field.kind == FK_GL) return run_step_of<PARTS, FieldGL, 0>(st, track, no_kernel);
+    if (st.args.field.kind == FK_M64) return run_step_of<PARTS, FieldM64, 1>(st, track, no_kernel);
+    return run_step_of<PARTS, FieldM32, 2>(st, track, no_kernel);
+}
+
+// ---- a plan on the host ----------------------------------------------------------------------------------------------------------
+// `count` words of the table form of value(i), in an exact-size malloc() block: a sanitizer's red zones sit where the plan's own
+// device allocation would end
+template <class Fn>
+void *table_form_words(size_t count, int word_bytes, uint64_t p, Fn &&value) {
+    void *t = malloc(count * (size_t) word_bytes);
+    if (!t) abort();
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t x = host::to_table_form(value(i), p, word_bytes);
+        if (word_bytes == 4) ((uint32_t *) t)[i] = (uint32_t) x;
+        else ((uint64_t *) t)[i] = x;
+    }
+    return t;
+}
+
+// What ntt_plan_create + ntt_plan_set_twiddles (T_plain: 2^logn plain residues) leave in a plan, and what ntt_plan_set_coset /
+// ntt_plan_set_coset_inverse add.  `target` sizes the launches of both pass kinds.  `inverse`: also the inverse table and, for
+// 8-byte words, the scaled stage-0 table; invertible = false when the table has an entry that is not a unit.
+struct HostPlan : PlanFacts {
+    bool invertible = false;
+    HostPlan(int word_bytes_, int logn_, uint64_t p_, const void *T_plain, uint32_t target, bool inverse) {
+        logn = logn_;
+        p = p_;
+        word_bytes = word_bytes_;
+        field = field_params(word_bytes, p);
+        ninv_plain = host::powmod(p / 2 + 1, (uint64_t) logn, p);
+        scale_tf = host::to_table_form(ninv_plain, p, word_bytes);
+        target_wgs = target_wgs_col = target;
+        const size_t N = (size_t) 1 << logn;
+        std::vector<uint64_t> T(N), Ti;
+        for (size_t i = 0; i < N; i++) T[i] = word_bytes == 4 ? ((const uint32_t *) T_plain)[i] : ((const uint64_t *) T_plain)[i];
+        tw_fwd = table_form_words(N, word_bytes, p, [&](size_t i) { return T[i]; });
+        if (!inverse || !host::invert_table(T, p, Ti)) return;
+        invertible = true;
+        tw_inv = table_form_words(N, word_bytes, p, [&](size_t i) { return Ti[i]; });
+        if (word_bytes == 8) tw_inv_sc = table_form_words(N / 2, 8, p, [&](size_t i) { return host::mulmod(Ti[N / 2 + i], ninv_plain, p); });
+    }
+    HostPlan(const HostPlan &) = delete;
+    ~HostPlan() {
+        for (void *b : {tw_fwd, tw_inv, tw_inv_sc, lde_s, cinv_u}) free(b);
+    }
+    // s[i] = shift^bitrev(i) over the N >> beta compact rows, periodic up to 4 words
+    void set_coset(int beta, uint64_t shift) {
+        const int ls = logn - beta;
+        const size_t ns = (size_t) 1 << ls;
+        free(lde_s);
+        lde_s = table_form_words(ns < 4 ? 4 : ns, word_bytes, p, [&](size_t i) { return host::powmod(shift, host::bitrev(i & (ns - 1), ls), p); });
+        lde_beta = beta;
+    }
+    // u[i] = shift^-bitrev(i) * N^-1, periodic up to 4 words; false when the shift is not a unit
+    bool set_coset_inverse(uint64_t shift) {
+        const uint64_t shift_inv = host::invmod(shift, p);
+        if (shift_inv == 0) return false;
+        const size_t N = (size_t) 1 << logn;
+        free(cinv_u);
+        cinv_u = table_form_words(N < 4 ? 4 : N, word_bytes, p, [&](size_t i) { return host::mulmod(host::powmod(shift_inv, host::bitrev(i & (N - 1), logn), p), ninv_plain, p); });
+        cinv_set = true;
+        return true;
+    }
+};
 
 }  // namespace emu

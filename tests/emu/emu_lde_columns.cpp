@@ -4,7 +4,7 @@
 // TEST INFRASTRUCTURE, a sibling of emu_columns.cpp: the same pass.h / plan.h / field.h the HIP kernels are built from, under g++,
 // every thread context of a workgroup stepped phase by phase, with the LDS hazard tracker on.  Every pass is the configuration the
 // launcher's own rule names (csrc/launch.h: mat_twin_dispatch) with the launcher's geometry and argument block (pass_geometry_of /
-// fill_pass_args), sequenced over plan.h's plan_column_passes exactly as ntt_api.hip's run_columns does.
+// fill_pass_args), and the launches are the library's own sequence (csrc/sequence.h: seq_columns over plan.h's plan_column_passes).
 //   * as a library (tests/emu_lde_columns_lib.py): emu_lde_columns() / emu_coset_inverse_columns() on the caller's buffers;
 //   * with -DEMU_LDE_COLUMNS_MAIN (tests/test_lde_columns_emu_asan.py, built with ASan + UBSan and linked with oracle/ntt_oracle.c):
 //     the sweep word classes x {lde, coset inverse} x logn x beta x width x pitch x count on malloc() buffers of EXACTLY
@@ -23,107 +23,19 @@ using namespace ntt::host;
 
 namespace {
 
-int ceil_log2(uint64_t x) {
-    int w = 0;
-    while (((uint64_t) 1 << w) < x) ++w;
-    return w;
-}
-
-uint64_t bitrev(uint64_t i, int bits) {
-    uint64_t r = 0;
-    for (int b = 0; b < bits; b++) r |= ((i >> b) & 1) << (bits - 1 - b);
-    return r;
-}
-
-void *table_form_copy(const std::vector<uint64_t> &v, uint64_t p, int word_bytes) {
-    void *t = malloc(v.size() * (size_t) word_bytes);  // exact-size heap buffer
-    if (!t) abort();
-    for (size_t i = 0; i < v.size(); i++) {
-        const uint64_t x = to_table_form(v[i], p, word_bytes);
-        if (word_bytes == 4) ((uint32_t *) t)[i] = (uint32_t) x;
-        else ((uint64_t *) t)[i] = x;
-    }
-    return t;
-}
-
-// kind 1: ntt_lde_columns (forward, the twin in the pass with stage 0 reads the compact source); 2: ntt_coset_inverse_columns
-template <class F>
-int run_twin(ErasedArgs e, int logn, int w, int kind, const void *in, uint32_t in_pitch, const void *vec, int beta) {
-    const std::vector<PassDesc> passes = plan_column_passes(logn);
-    if (passes.empty()) return -3;
-    const bool inverse = kind == 2;
-    const void *cur = in;
-    for (size_t k = 0; k < passes.size(); k++) {
-        const PassDesc &pd = passes[inverse ? passes.size() - 1 - k : k];
-        ErasedArgs a = e;
-        a.in = cur;
-        a.n = logn + w;
-        a.s0 = pd.s0 + w;
-        if (kind == 1 && pd.s0 == 0) {
-            a.in = e.out;
-            a.mat_lde_in = in;
-            a.mat_lde_s = vec;
-            a.mat_lde_beta = beta;
-            a.mat_src_pitch = in_pitch;
-        }
-        if (kind == 2 && pd.s0 == 0) a.mat_cinv_u = vec;
-        int rc = -2;  // no such kernel
-        if (inverse) mat_twin_dispatch<F, true>(pd.log_m, a, [&](auto tag) { rc = emu::run_pass_launch<typename decltype(tag)::Cfg>(a, true); });
-        else mat_twin_dispatch<F, false>(pd.log_m, a, [&](auto tag) { rc = emu::run_pass_launch<typename decltype(tag)::Cfg>(a, true); });
-        if (rc) return rc;
-        cur = e.out;
-    }
-    return 0;
-}
-
-int run_any(int word_bytes, int logn, uint64_t p, const void *T_plain, int kind, const void *in, uint32_t in_pitch, void *out, uint32_t pitch,
+// kind COL_LDE: ntt_lde_columns (forward, the twin in the pass with stage 0 reads the compact source); COL_CINV: ntt_coset_inverse_columns
+int run_any(int word_bytes, int logn, uint64_t p, const void *T_plain, ColKind kind, const void *in, uint32_t in_pitch, void *out, uint32_t pitch,
             uint32_t width, uint32_t count, int beta, uint64_t shift, uint32_t target_wgs) {
     if (width == 0 || count == 0) return 0;
     if (width > pitch || width > in_pitch) return -1;
-    const size_t N = (size_t) 1 << logn;
-    std::vector<uint64_t> T(N), Ti;
-    for (size_t i = 0; i < N; i++) T[i] = word_bytes == 4 ? ((const uint32_t *) T_plain)[i] : ((const uint64_t *) T_plain)[i];
-    if (kind == 2 && !invert_table(T, p, Ti)) return -5;
-    void *tw = table_form_copy(kind == 2 ? Ti : T, p, word_bytes);
-    // the plan's vector: s[i] = shift^bitrev(i) over the compact rows (periodic up to 4 words), or u[i] = shift^-bitrev(i) * N^-1
-    std::vector<uint64_t> vec;
-    if (kind == 1) {
-        const int ls = logn - beta;
-        const size_t ns = (size_t) 1 << ls, len = ns < 4 ? 4 : ns;
-        vec.resize(len);
-        for (size_t i = 0; i < len; i++) vec[i] = powmod(shift, bitrev(i & (ns - 1), ls), p);
-    } else {
-        const uint64_t si = powmod(shift, p - 2, p), ninv = powmod(p / 2 + 1, (uint64_t) logn, p);  // prime moduli in the tests
-        vec.resize(N);
-        for (size_t i = 0; i < N; i++) vec[i] = mulmod(powmod(si, bitrev(i, logn), p), ninv, p);
-    }
-    void *dvec = table_form_copy(vec, p, word_bytes);
-    const int log_c = col_log_c(word_bytes);
-    const int w = ceil_log2(width) > log_c ? ceil_log2(width) : log_c;
-    ErasedArgs e;
-    memset(&e, 0, sizeof(e));
-    e.field = field_params(word_bytes, p);
-    e.out = out;
-    e.tw = tw;
-    e.batch = count;
-    e.layout = LAYOUT_NATURAL;
-    e.target_wgs = target_wgs;
-    e.mat_w = w;
-    e.mat_pitch = pitch;
-    e.mat_width = width;
-    int rc = -100;
-#if EMU_LDE_COLUMNS_FIELDS & 1
-    if (e.field.kind == FK_GL) rc = run_twin<FieldGL>(e, logn, w, kind, in, in_pitch, dvec, beta);
-#endif
-#if EMU_LDE_COLUMNS_FIELDS & 2
-    if (e.field.kind == FK_M64) rc = run_twin<FieldM64>(e, logn, w, kind, in, in_pitch, dvec, beta);
-#endif
-#if EMU_LDE_COLUMNS_FIELDS & 4
-    if (e.field.kind == FK_M32) rc = run_twin<FieldM32>(e, logn, w, kind, in, in_pitch, dvec, beta);
-#endif
-    free(tw);
-    free(dvec);
-    return rc;
+    emu::HostPlan pl(word_bytes, logn, p, T_plain, target_wgs, kind == COL_CINV);
+    if (kind == COL_CINV && (!pl.invertible || !pl.set_coset_inverse(shift))) return -5;
+    if (kind == COL_LDE) pl.set_coset(beta, shift);
+    const std::vector<PassDesc> passes = plan_column_passes(logn);
+    if (passes.empty()) return -3;
+    return seq_columns(pl, passes, kind, in, in_pitch, out, pitch, width, count, kind == COL_CINV, 0, [](const Step &st) {
+        return emu::run_step<emu::field_parts(EMU_LDE_COLUMNS_FIELDS, emu::PARTS_MAT, 3)>(st, true, -2);
+    });
 }
 
 }  // namespace
@@ -135,13 +47,13 @@ extern "C" {
 int emu_lde_columns(int word_bytes, int logn, uint64_t p, const void *T_plain, const void *in, uint32_t in_pitch, void *out, uint32_t out_pitch,
                     uint32_t width, uint32_t count, int beta, uint64_t shift, uint32_t target_wgs) {
     if (beta < 1 || beta > 4 || beta >= logn) return -1;
-    return run_any(word_bytes, logn, p, T_plain, 1, in, in_pitch, out, out_pitch, width, count, beta, shift, target_wgs);
+    return run_any(word_bytes, logn, p, T_plain, COL_LDE, in, in_pitch, out, out_pitch, width, count, beta, shift, target_wgs);
 }
 
 // ntt_coset_inverse_columns; in, out: (count * M - 1) * pitch + width words (out may be in)
 int emu_coset_inverse_columns(int word_bytes, int logn, uint64_t p, const void *T_plain, const void *in, void *out, uint32_t width, uint32_t pitch,
                               uint32_t count, uint64_t shift, uint32_t target_wgs) {
-    return run_any(word_bytes, logn, p, T_plain, 2, in, pitch, out, pitch, width, count, 0, shift, target_wgs);
+    return run_any(word_bytes, logn, p, T_plain, COL_CINV, in, pitch, out, pitch, width, count, 0, shift, target_wgs);
 }
 
 // The launcher's refusals (launch.h: fill_pass_args), asked on one shape (logn 12, w 5, passes 6 + 6).  A set bit = refused as it
@@ -271,29 +183,11 @@ int emu_lde_columns_refusals(void) {
 }  // extern "C"
 
 #if defined(EMU_LDE_COLUMNS_MAIN)
-#include "../../oracle/ntt_oracle.h"
+#include "emu_sweep.h"
 
 namespace {
 
-uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-uint64_t rnd() {
-    rng_state ^= rng_state << 13;
-    rng_state ^= rng_state >> 7;
-    rng_state ^= rng_state << 17;
-    return rng_state;
-}
-
-struct Class {
-    const char *name;
-    int wb;
-    uint64_t p, g;
-};
-
-uint64_t get(const void *b, int wb, size_t i) { return wb == 4 ? ((const uint32_t *) b)[i] : ((const uint64_t *) b)[i]; }
-void put(void *b, int wb, size_t i, uint64_t v) {
-    if (wb == 4) ((uint32_t *) b)[i] = (uint32_t) v;
-    else ((uint64_t *) b)[i] = v;
-}
+using namespace sweep;
 
 // one case on exact-size buffers; kind 1 lde (beta >= 1, out of place), 2 coset inverse (beta ignored); returns 0 when every live
 // word equals the oracle's and every padding word is untouched
@@ -302,11 +196,10 @@ int one_case(const Class &c, int logn, int beta, uint32_t width, uint32_t in_pit
     const size_t M = (size_t) 1 << logn, wb = (size_t) c.wb, rows_in = kind == 1 ? M >> beta : M;
     const size_t in_words = ((size_t) count * rows_in - 1) * in_pitch + width, out_words = ((size_t) count * M - 1) * pitch + width;
     const uint64_t sentinel = c.wb == 4 ? 0xFFFFFFF5ull : 0xFFFFFFFFFFFFFFF5ull;  // >= p for every class
-    std::vector<uint64_t> T64(M);
-    if (oracle_make_table_u64(1, M, T64.data(), c.p, c.g) != 0) return 0;  // 2^logn does not divide p - 1: no such case
-    void *T = malloc(M * wb), *in = malloc(in_words * wb), *out = in_place ? in : malloc(out_words * wb), *cols = malloc((size_t) count * width * M * wb);
-    if (!T || !in || !out || !cols) abort();
-    for (size_t i = 0; i < M; i++) put(T, c.wb, i, T64[i]);
+    void *T = oracle_table(c, M);
+    if (!T) return 0;  // 2^logn does not divide p - 1: no such case
+    void *in = malloc(in_words * wb), *out = in_place ? in : malloc(out_words * wb), *cols = malloc((size_t) count * width * M * wb);
+    if (!in || !out || !cols) abort();
     for (size_t i = 0; i < in_words; i++) put(in, c.wb, i, sentinel ^ (i & 3));  // padding: non-canonical junk
     if (!in_place)
         for (size_t i = 0; i < out_words; i++) put(out, c.wb, i, sentinel);
@@ -316,8 +209,7 @@ int one_case(const Class &c, int logn, int beta, uint32_t width, uint32_t in_pit
     for (size_t m = 0; m < count; m++)
         for (size_t r = 0; r < rows_in; r++)
             for (size_t k = 0; k < width; k++) {
-                const uint64_t rr = rnd();
-                const uint64_t x = (rr & 15) == 0 ? 0 : (rr & 15) == 1 ? c.p - 1 : (rr >> 4) % c.p;
+                const uint64_t x = rnd_residue(c.p);
                 put(in, c.wb, (m * rows_in + r) * in_pitch + k, x);
                 if (kind == 1) put(cols, c.wb, (m * width + k) * M + (r << beta), mulmod(x, powmod(shift, bitrev(r, ls), c.p), c.p));
                 else put(cols, c.wb, (m * width + k) * M + r, x);
@@ -325,13 +217,9 @@ int one_case(const Class &c, int logn, int beta, uint32_t width, uint32_t in_pit
     void *in0 = malloc(in_words * wb);
     if (!in0) abort();
     memcpy(in0, in, in_words * wb);
-    int orc = 0;
     const size_t nb = (size_t) count * width;
-    if (kind == 1 && c.wb == 4) oracle_ntt_batch_u32((uint32_t *) cols, (uint32_t) M, nb, (const uint32_t *) T, (uint32_t) c.p, 1);
-    else if (kind == 1) oracle_ntt_batch_u64((uint64_t *) cols, M, nb, (const uint64_t *) T, c.p, 1);
-    else {
-        orc = c.wb == 4 ? oracle_intt_batch_u32((uint32_t *) cols, (uint32_t) M, nb, (const uint32_t *) T, (uint32_t) c.p, 1)
-                        : oracle_intt_batch_u64((uint64_t *) cols, M, nb, (const uint64_t *) T, c.p, 1);
+    const int orc = oracle_transform(c, cols, M, nb, T, kind == 2);
+    if (kind == 2) {
         const uint64_t si = powmod(shift, c.p - 2, c.p);
         for (size_t b = 0; b < nb; b++)
             for (size_t r = 0; r < M; r++) put(cols, c.wb, b * M + r, mulmod(get(cols, c.wb, b * M + r), powmod(si, bitrev(r, logn), c.p), c.p));
@@ -361,19 +249,14 @@ int one_case(const Class &c, int logn, int beta, uint32_t width, uint32_t in_pit
 
 // usage: emu_lde_columns_sweep <class: gl | m64 | m32>
 int main(int argc, char **argv) {
-    const Class classes[] = {
-        {"gl", 8, GOLDILOCKS, 7},
-        {"m64", 8, 0xFFFFFFFC00000001ull, 10},  // general 64-bit class: an NTT prime above 2^63 (sums wrap: the carry paths)
-        {"m32", 4, 998244353ull, 3},
-    };
     if (argc < 2) return 2;
     long cases = 0, bad = 0;
     if (emu_lde_columns_refusals() != 0x1FFF) {
         fprintf(stderr, "refusals: %#x\n", emu_lde_columns_refusals());
         bad++;
     }
-    for (const Class &c : classes) {
-        if (strcmp(c.name, argv[1]) != 0) continue;
+    if (const Class *cp = find_class(argv[1])) {
+        const Class &c = *cp;
         const uint64_t shifts[] = {1, c.g, c.p - 1};
         const int logns[] = {4, 5, 8, 9, 12};
         const uint32_t widths[] = {1, 3, 16, 17, 33};
@@ -413,8 +296,6 @@ int main(int argc, char **argv) {
         bad += one_case(c, 17, 0, 17, 18, 18, 1, 2, true, 16384, c.g);
         cases += 3;
     }
-    printf("%s: %ld cases, %ld bad\n", argv[1], cases, bad);
-    if (bad == 0 && cases > 0) printf("%s: %ld cases clean\n", argv[1], cases);
-    return bad ? 1 : (cases ? 0 : 3);
+    return report(argv[1], cases, bad);
 }
 #endif

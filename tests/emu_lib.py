@@ -14,7 +14,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        deps = [SRC, os.path.join(HERE, "emu", "emu_exec.h")] + [os.path.join(CSRC, f) for f in ("pass.h", "field.h", "plan.h", "launch.h")]
+        deps = [SRC, os.path.join(HERE, "emu", "emu_exec.h")] + [os.path.join(CSRC, f) for f in ("pass.h", "field.h", "plan.h", "launch.h", "sequence.h")]
         if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", SRC, "-o", OUT])
         L = C.CDLL(OUT)
@@ -23,6 +23,7 @@ def lib():
         L.emu_forward_product.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_uint32, C.c_uint64, C.c_uint32]
         L.emu_polymul_fused.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.emu_sequence.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int), C.c_int]
         L.emu_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.emu_geometry.argtypes = [C.c_int] * 6 + [C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]
         for n in ("emu_gl_mul", "emu_gl_add", "emu_gl_sub"):

@@ -215,10 +215,10 @@ def test_error_contract_without_a_device():
 
 
 def _library_column_target():
-    """the workgroup count the library sizes its column launches for: the initialiser of target_wgs_col in ntt_api.hip"""
-    src = open(os.path.join(ROOT, "ntt_aie_amd", "csrc", "ntt_api.hip")).read()
+    """the workgroup count the library sizes its column launches for: the initialiser of target_wgs_col in the plan facts (sequence.h)"""
+    src = open(os.path.join(ROOT, "ntt_aie_amd", "csrc", "sequence.h")).read()
     m = re.search(r"^\s*uint32_t\s+target_wgs_col\s*=\s*([0-9][0-9\s*]*);", src, re.M)
-    assert m, "the initialiser of target_wgs_col was not found in ntt_api.hip"
+    assert m, "the initialiser of target_wgs_col was not found in sequence.h"
     target = 1
     for f in m.group(1).split("*"):
         target *= int(f)
