@@ -11,9 +11,16 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 GOLD = 0xFFFFFFFF00000001
-# the four word classes of tests/test_gpu_coset_inverse.py; the reference's own modulus has kind-1 tables up to 2^8 only, larger sizes
+# the four word classes every coset / column GPU file started from; the reference's own modulus has kind-1 tables up to 2^8 only, larger sizes
 # take the reference's kind-0 rule (the entry points are defined at network level, for any invertible table)
 CLASSES = {"gl": (8, GOLD, 7), "m64": (8, 0xFFFFFFFC00000001, 10), "m32": (4, 998244353, 3), "kyber": (4, 3329, 3)}
+# 4-byte words run one of three instruction streams, chosen per launch from the modulus (pass_kernel.inc): 0 "lazy" below 2^30 -- both
+# 4-byte classes above --, 1 "small" in [2^30, 2^31), 2 "any" from 2^31 on.  These classes take the coset and column kernels through the
+# other two; every helper of the coset / column GPU files resolves a class name in ALL_CLASSES, and this is the one definition
+STREAM_CLASSES = {"bb31": (4, 2013265921, 31),   # 15*2^27 + 1, stream 1, two-adicity 27
+                  "kb31": (4, 2130706433, 3),    # 2^31 - 2^24 + 1, stream 1 at its upper edge, two-adicity 24
+                  "top32": (4, 4293918721, 19)}  # 2^32 - 2^20 + 1, stream 2 where almost every sum carries, two-adicity 20
+ALL_CLASSES = {**CLASSES, **STREAM_CLASSES}
 # (logn, width, pitch, count): one pass with several matrices per workgroup (width 17 gives w = 5: 16 matrices of 4-byte words, 8 of
 # 8-byte words) and a count that leaves the last group partly empty; 5 + 4; 7 + 6; 8 + 8 (wave-uniform twiddles) at a line-aligned and
 # at an odd pitch
@@ -24,7 +31,7 @@ SHAPES = [(4, 17, 18, 19), (9, 3, 3, 3), (13, 33, 48, 1), (16, 100, 128, 1), (16
 def _table_cached(logn, cls):
     import oracle_py
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     n = 1 << logn
     T = oracle_py.make_table(1, n, p, g, wb) if (p - 1) % n == 0 else oracle_py.make_roots(n, p, g, wb)
     T.setflags(write=False)
@@ -36,7 +43,7 @@ def _case(cls, logn, width, count):
     """inputs [count][N][width] and the oracle's three transforms of their columns, computed once and shared (read-only)"""
     import oracle_py
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     n = 1 << logn
     T = _table_cached(logn, cls)
@@ -56,7 +63,7 @@ def _case(cls, logn, width, count):
 def _plan(logn, cls):
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     pl = eng.NTTPlan(logn, p, wb, 0)
     pl.set_twiddles(np.array(_table_cached(logn, cls)))
     return pl
@@ -71,7 +78,7 @@ def test_columns_decomposition_is_reported(oracle):
         pl.close()
 
 
-@pytest.mark.parametrize("cls", sorted(CLASSES))
+@pytest.mark.parametrize("cls", sorted(ALL_CLASSES))
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "n%d_w%d_p%d_c%d" % s)
 def test_columns_against_the_oracle_with_guard_words(oracle, cls, shape):
     """forward, scaled and unscaled inverse, out of place and in place.  Input and output each sit in the middle of one allocation:
@@ -82,7 +89,7 @@ def test_columns_against_the_oracle_with_guard_words(oracle, cls, shape):
     import ntt_aie_amd as eng
     from ntt_aie_amd import _lib
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, width, pitch, count = shape
     n = 1 << logn
     tdt = torch.int32 if wb == 4 else torch.int64
@@ -118,7 +125,7 @@ def test_columns_against_the_oracle_with_guard_words(oracle, cls, shape):
     pl.close()
 
 
-@pytest.mark.parametrize("cls", ["gl", "m32"])
+@pytest.mark.parametrize("cls", ["gl", "m32", "bb31"])
 def test_wrapper_round_trip_on_a_strided_view(oracle, cls):
     """NTTPlan.forward_columns / inverse_columns on big[:, :, :width] of a larger tensor: accepted as it is, in place and with an
     allocated result; inverse(forward(x)) == x; plan.forward on the transposed copy agrees (second witness)"""
@@ -126,7 +133,7 @@ def test_wrapper_round_trip_on_a_strided_view(oracle, cls):
 
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, width, count = 13, 33, 1
     n = 1 << logn
     ref = _case(cls, logn, width, count)

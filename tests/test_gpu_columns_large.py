@@ -11,7 +11,7 @@ import pytest
 
 import test_gpu_columns as TC
 import test_gpu_lde_columns as TL
-from test_gpu_columns import CLASSES, GOLD
+from test_gpu_columns import ALL_CLASSES, CLASSES, GOLD, STREAM_CLASSES
 
 pytestmark = pytest.mark.gpu
 
@@ -19,6 +19,16 @@ pytestmark = pytest.mark.gpu
 THREE_PASS_SHAPES = [(17, 3, 3, 2), (17, 33, 48, 1), (20, 2, 5, 1)]
 # (logm, beta, width, in_pitch, out_pitch, count): in_pitch != out_pitch, one of them odd
 THREE_PASS_LDE_SHAPES = [(17, 1, 3, 3, 4, 2), (17, 4, 33, 40, 33, 1), (20, 3, 2, 5, 4, 1)]
+_PLAIN_ID, _LDE_ID = (lambda s: "n%d_w%d_p%d_c%d" % s), (lambda s: "m%d_b%d_w%d_ip%d_op%d_c%d" % s)
+
+
+def _three_pass_params(shapes, ident):
+    """every shape for the four classes of CLASSES (ids as two stacked parametrisations give them); for the three 4-byte classes of the
+    other two instruction streams the logn-17 shapes only: there the plain in-place pass in the middle runs in streams 1 and 2"""
+    return ([pytest.param(cls, s, id="%s-%s" % (ident(s), cls)) for cls in sorted(CLASSES) for s in shapes]
+            + [pytest.param(cls, s, id="%s-%s" % (ident(s), cls)) for cls in sorted(STREAM_CLASSES) for s in shapes if s[0] == 17])
+
+
 # ---- B2: the size limit at equality: N * pitch == 2^28 words
 LIMIT_LOGN, LIMIT_PITCH = 20, 256
 # ---- B3: (logn, width, pitch, count) with so many matrices that, at the library's own column target, every pass streams two groups
@@ -63,7 +73,7 @@ def _check_plain(cls, shape, ref, pl, names, out_of_place=True, in_place=True):
     """ntt_forward_columns / ntt_inverse_columns on guarded buffers against ref[name]"""
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, width, pitch, count = shape
     gin, gout = TL._Guarded(1 << logn, pitch, width, count, -3, _tdt(wb)), None
     calls = _plain_calls(pl, width, pitch, count)
@@ -87,7 +97,7 @@ def _check_lde(cls, shape, x, want, pl):
     import ntt_aie_amd as eng
     from ntt_aie_amd import _lib
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logm, beta, width, in_pitch, out_pitch, count = shape
     gin = TL._Guarded((1 << logm) >> beta, in_pitch, width, count, -3, _tdt(wb))
     gout = TL._Guarded(1 << logm, out_pitch, width, count, -5, _tdt(wb))
@@ -103,7 +113,7 @@ def _check_cinv(cls, shape, x, want, pl, out_of_place=True, in_place=True):
     import ntt_aie_amd as eng
     from ntt_aie_amd import _lib
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, width, pitch, count = shape
     call = lambda a, b: _lib.lib().ntt_coset_inverse_columns(pl._h, a, b, width, pitch, count, None)
     gin = TL._Guarded(1 << logn, pitch, width, count, -3, _tdt(wb))
@@ -126,8 +136,7 @@ def _three(pl, shape):
 
 
 # ---- B1 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("cls", sorted(CLASSES))
-@pytest.mark.parametrize("shape", THREE_PASS_SHAPES, ids=lambda s: "n%d_w%d_p%d_c%d" % s)
+@pytest.mark.parametrize("cls,shape", _three_pass_params(THREE_PASS_SHAPES, _PLAIN_ID))
 def test_three_passes_against_the_oracle(oracle, cls, shape):
     """forward, scaled and unscaled inverse, out of place and in place: the middle pass has several hi blocks, a first stage above
     mat_w and a row stride above 1 at once, and neither reads the caller's input nor holds stage 0"""
@@ -137,8 +146,7 @@ def test_three_passes_against_the_oracle(oracle, cls, shape):
     pl.close()
 
 
-@pytest.mark.parametrize("cls", sorted(CLASSES))
-@pytest.mark.parametrize("shape", THREE_PASS_LDE_SHAPES, ids=lambda s: "m%d_b%d_w%d_ip%d_op%d_c%d" % s)
+@pytest.mark.parametrize("cls,shape", _three_pass_params(THREE_PASS_LDE_SHAPES, _LDE_ID))
 def test_three_pass_lde_columns_against_the_oracle(oracle, cls, shape):
     """the fused first pass (compact source in), then two plain in-place passes"""
     logm, beta, width, in_pitch, out_pitch, count = shape
@@ -151,8 +159,7 @@ def test_three_pass_lde_columns_against_the_oracle(oracle, cls, shape):
     pl.close()
 
 
-@pytest.mark.parametrize("cls", sorted(CLASSES))
-@pytest.mark.parametrize("shape", THREE_PASS_SHAPES, ids=lambda s: "n%d_w%d_p%d_c%d" % s)
+@pytest.mark.parametrize("cls,shape", _three_pass_params(THREE_PASS_SHAPES, _PLAIN_ID))
 def test_three_pass_coset_inverse_columns_against_the_oracle(oracle, cls, shape):
     """two plain passes, then the fused last pass (row r times u[r]); out of place and in place"""
     logn, width, pitch, count = shape
@@ -201,7 +208,7 @@ def test_a_matrix_of_exactly_2_to_the_28_words(oracle, cls):
     import ntt_aie_amd as eng
     from ntt_aie_amd import _lib
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, pitch, width = LIMIT_LOGN, LIMIT_PITCH, 2
     n = 1 << logn
     assert n * pitch == 1 << 28
@@ -258,7 +265,7 @@ def test_the_limit_with_129_live_columns(oracle):
     from ntt_aie_amd import _lib
 
     cls, width = "gl", 129
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, pitch = LIMIT_LOGN, LIMIT_PITCH
     n = 1 << logn
     T = TC._table_cached(logn, cls)
@@ -313,8 +320,10 @@ def test_batch_loop_and_taper(oracle, cls, shape):
 # ---- B4 ---------------------------------------------------------------------------------------------------------------------
 def _edge_matrix(cls, rows, width, seed):
     """[1][rows][width]: columns of all p - 1, all 0, all 1, alternating 0 / p - 1, p - 1 in row 0 only, p - 1 in the last row only;
-    for 8-byte words also columns of 2^32 - 1, 2^32, 2^63 and p - 2^32 (mod p); the other columns are random"""
-    wb, p, g = CLASSES[cls]
+    for 8-byte words also columns of 2^32 - 1, 2^32, 2^63 and p - 2^32 (mod p); for 4-byte words columns of 2^30, 2^31 - 1, 2^31,
+    (p - 1) / 2 and (p + 1) / 2 (mod p) -- where a sum first reaches 2^31 and 2^32: the `small` stream's v_min corrections and the `any`
+    stream's carry selects change arm there; the other columns are random"""
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     x = (np.random.default_rng(seed).integers(0, 2**63, size=(1, rows, width), dtype=np.uint64) % np.uint64(p)).astype(dt)
     m = x[0]
@@ -322,19 +331,19 @@ def _edge_matrix(cls, rows, width, seed):
     m[0::2, 3], m[1::2, 3] = 0, p - 1
     m[:, 4], m[0, 4] = 0, p - 1
     m[:, 5], m[-1, 5] = 0, p - 1
-    fills = [v % p for v in (2**32 - 1, 2**32, 2**63, p - 2**32)] if wb == 8 else []
+    fills = [v % p for v in ((2**32 - 1, 2**32, 2**63, p - 2**32) if wb == 8 else (2**30, 2**31 - 1, 2**31, (p - 1) // 2, (p + 1) // 2))]
     for i, v in enumerate(fills):
         m[:, 6 + i] = v
     assert 6 + len(fills) < width
     return x
 
 
-@pytest.mark.parametrize("cls", sorted(CLASSES))
+@pytest.mark.parametrize("cls", sorted(ALL_CLASSES))
 def test_columns_of_edge_residues(oracle, cls):
     """forward, scaled inverse, the LDE (beta 1) and the coset inverse with the shifts p - 1 and g, on a matrix whose first columns
     are the residues at which the arithmetic can go wrong: the multiplications by s[row >> beta] in the fused LDE load and by u[row]
     before the fused coset-inverse store see them as well as the butterflies"""
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     logn, width, pitch, count = EDGE_SHAPE
     n, beta = 1 << logn, 1
@@ -362,7 +371,7 @@ def test_columns_of_edge_residues(oracle, cls):
 def _plumbing(cls):
     """plan with twiddles, coset (beta 3, shift g) and coset-inverse (shift g) set; inputs and the oracle's words of all four entry
     points at PLUMBING_SHAPE"""
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, width, pitch = PLUMBING_SHAPE
     pl = TL._plan(logn, cls)
     pl.set_coset(3, g)
@@ -409,7 +418,7 @@ def _all_four(pl, r, pitch, tdt, key):
 def test_clone_carries_the_column_configuration(oracle, cls):
     """the clone owns its coset and coset-inverse vectors: changing both on the source does not reach lde_columns /
     coset_inverse_columns of the clone, and forward_columns / inverse_columns give the oracle's words there too"""
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     pl, r = _plumbing(cls)
     cl = pl.clone()
     assert cl.column_passes == pl.column_passes and cl.log_blowup == 3 and cl.coset_inverse_set
@@ -428,7 +437,7 @@ def test_graph_capture_of_the_column_entry_points(oracle, cls):
 
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, width, pitch = PLUMBING_SHAPE
     tdt = _tdt(wb)
     pl, r = _plumbing(cls)
@@ -467,7 +476,7 @@ def test_graph_capture_of_the_column_entry_points(oracle, cls):
 def test_a_pinned_policy_leaves_the_columns_alone(oracle, cls):
     """include/ntt_hip.h: the columns decomposition is fixed by logn.  Under every pinned alternative of the plan column_passes is
     unchanged and all four entry points give the oracle's words"""
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     pl, r = _plumbing(cls)
     passes = pl.column_passes
     alts = pl.alternatives
@@ -494,7 +503,7 @@ def test_columns_of_a_shared_plan_from_two_host_threads(oracle, cls):
 
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, width, pitch = PLUMBING_SHAPE
     pl, r = _plumbing(cls)
     dt = np.uint32 if wb == 4 else np.uint64

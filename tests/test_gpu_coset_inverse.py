@@ -9,13 +9,14 @@ import functools
 import numpy as np
 import pytest
 
+from test_gpu_columns import ALL_CLASSES, CLASSES, GOLD, STREAM_CLASSES  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-GOLD = 0xFFFFFFFF00000001
-# the four word classes of tests/test_gpu_lde.py: Goldilocks, a general 64-bit NTT prime above 2^63, a lazy 4-byte NTT prime, the
+# the word classes of tests/test_gpu_lde.py, defined once in tests/test_gpu_columns.py.  CLASSES: Goldilocks, a general 64-bit NTT prime above 2^63, a lazy 4-byte NTT prime, the
 # reference's own modulus (p - 1 = 2^8 * 13: kind-1 tables exist up to 2^8 only, larger sizes take the reference's kind-0 rule --
-# ntt_coset_inverse is defined at network level, for any invertible table)
-CLASSES = {"gl": (8, GOLD, 7), "m64": (8, 0xFFFFFFFC00000001, 10), "m32": (4, 998244353, 3), "kyber": (4, 3329, 3)}
+# ntt_coset_inverse is defined at network level, for any invertible table).  STREAM_CLASSES: three more 4-byte moduli for the other two
+# instruction streams of 4-byte words
 FUSED_FROM = 5  # the documented rule of ntt_plan_info 12
 
 
@@ -72,7 +73,7 @@ def _inputs(batch, n, p, dt, seed):
 def _plan(oracle, logm, cls):
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     T = _table(oracle, logm, wb, p, g)
     pl = eng.NTTPlan(logm, p, wb, 0)
     pl.set_twiddles(T)
@@ -82,7 +83,7 @@ def _plan(oracle, logm, cls):
 def test_pointwise_comparator_is_python_integers(oracle):
     """the oracle's pointwise product used by _expected, against Python integers (so the comparator is what the issue states)"""
     for cls in sorted(CLASSES):
-        wb, p, g = CLASSES[cls]
+        wb, p, g = ALL_CLASSES[cls]
         dt = np.uint32 if wb == 4 else np.uint64
         y = _inputs(2, 64, p, dt, 1)
         T = _table(oracle, 6, wb, p, g)
@@ -92,7 +93,7 @@ def test_pointwise_comparator_is_python_integers(oracle):
         assert _expected(oracle, y, T, p, g).tolist() == want
 
 
-@pytest.mark.parametrize("cls", sorted(CLASSES))
+@pytest.mark.parametrize("cls", sorted(ALL_CLASSES))
 @pytest.mark.parametrize("logm", [1, 2, 3, 4, 5, 6, 9, 11, 13, 14, 16])
 def test_coset_inverse_sweep(oracle, cls, logm):
     """word classes x sizes (unfused below 2^5; single-pass; two-pass) x batch 1 / 5 / 33 x both input layouts from 2^4, shift
@@ -100,7 +101,7 @@ def test_coset_inverse_sweep(oracle, cls, logm):
     and in place; ntt_plan_info 12 follows the documented rule; the other transforms of the plan are unaffected by the setting"""
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     m = 1 << logm
     pl, T = _plan(oracle, logm, cls)
@@ -143,11 +144,13 @@ def test_coset_inverse_sweep(oracle, cls, logm):
     pl.close()
 
 
-def test_coset_inverse_three_pass_plan(oracle):
-    """a three-pass decomposition: 4-byte words, p >= 2^30, 2^22 = 8 + 7 + 7 (pinned), batch 2 -- the shape of test_lde_three_pass_plan"""
+@pytest.mark.parametrize("p,g", [(3221225473, 5), (2013265921, 31)], ids=["p3221225473", "bb31"])
+def test_coset_inverse_three_pass_plan(oracle, p, g):
+    """a three-pass decomposition: 4-byte words, p >= 2^30 (above 2^31, and BabyBear below it), 2^22 = 8 + 7 + 7 (pinned), batch 2 --
+    the shape of test_lde_three_pass_plan"""
     import ntt_aie_amd as eng
 
-    p, g, logm, batch = 3221225473, 5, 22, 2
+    logm, batch = 22, 2
     T = oracle.make_table(1, 1 << logm, p, g, 4)
     pl = eng.NTTPlan(logm, p, 4, 0)
     pl.set_twiddles(T)
@@ -165,12 +168,12 @@ def test_coset_inverse_three_pass_plan(oracle):
     pl.close()
 
 
-@pytest.mark.parametrize("cls,logn,beta", [("gl", 9, 2), ("m32", 8, 4)])
+@pytest.mark.parametrize("cls,logn,beta", [("gl", 9, 2), ("m32", 8, 4), ("bb31", 8, 4), ("top32", 9, 2)])
 def test_round_trip_with_lde(oracle, cls, logn, beta):
     """coset_inverse(lde(c)) is the zero-interleaved c, both layouts between the two calls: the prover's pair is closed"""
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     logm = logn + beta
     pl, T = _plan(oracle, logm, cls)
@@ -189,8 +192,8 @@ def test_round_trip_with_lde(oracle, cls, logn, beta):
     pl.close()
 
 
-@pytest.mark.parametrize("cls", ["gl", "m32"])
-@pytest.mark.parametrize("logm", [5, 8, 12, 13])
+@pytest.mark.parametrize("logm,cls", [pytest.param(logm, cls, id="%d-%s" % (logm, cls)) for cls, sizes in
+                                      (("gl", (5, 8, 12, 13)), ("m32", (5, 8, 12, 13)), ("bb31", (12, 13)), ("top32", (12, 13))) for logm in sizes])
 def test_coset_inverse_stays_inside_the_callers_buffers(oracle, cls, logm):
     """memory safety on hardware: d_in and d_out each carved out of a larger allocation with sentinel words directly before and
     after, ragged batches (a last polynomial group that is part empty where a workgroup holds several polynomials); the sentinels
@@ -199,7 +202,7 @@ def test_coset_inverse_stays_inside_the_callers_buffers(oracle, cls, logm):
 
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     tdt = torch.int32 if wb == 4 else torch.int64
     pl, T = _plan(oracle, logm, cls)

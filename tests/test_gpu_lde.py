@@ -6,13 +6,14 @@ Every result is compared word for word with the ORACLE's network applied to the 
 import numpy as np
 import pytest
 
+from test_gpu_columns import ALL_CLASSES, CLASSES, GOLD, STREAM_CLASSES  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-GOLD = 0xFFFFFFFF00000001
-# word class -> (word bytes, p, generator): Goldilocks, a general 64-bit NTT prime above 2^63, a lazy 4-byte NTT prime, the
+# word class -> (word bytes, p, generator), defined once in tests/test_gpu_columns.py.  CLASSES: Goldilocks, a general 64-bit NTT prime above 2^63, a lazy 4-byte NTT prime, the
 # reference's own modulus (p - 1 = 2^8 * 13: kind-1 tables exist up to 2^8 only, larger sizes take the reference's kind-0 rule --
-# ntt_lde is defined at network level, for any table)
-CLASSES = {"gl": (8, GOLD, 7), "m64": (8, 0xFFFFFFFC00000001, 10), "m32": (4, 998244353, 3), "kyber": (4, 3329, 3)}
+# ntt_lde is defined at network level, for any table).  STREAM_CLASSES: three more 4-byte moduli, in [2^30, 2^31) and above 2^31, which
+# take the kernels through the other two instruction streams of 4-byte words
 
 
 def _bitrev(i, bits):
@@ -62,21 +63,21 @@ def _inputs(batch, n, p, dt, seed):
 def _plan(oracle, logm, cls):
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     T = _table(oracle, logm, wb, p, g)
     pl = eng.NTTPlan(logm, p, wb, 0)
     pl.set_twiddles(T)
     return pl, T
 
 
-@pytest.mark.parametrize("cls", sorted(CLASSES))
+@pytest.mark.parametrize("cls", sorted(ALL_CLASSES))
 @pytest.mark.parametrize("logm", [3, 4, 5, 6, 9, 11, 13, 14, 16])
 def test_lde_sweep(oracle, cls, logm):
     """word classes x sizes (unfused below 2^5; single-pass; two-pass) x blow-up 1..4 x batch 1 / 5 / 33 x both layouts, shift
     cycling through {1, g, p - 1}, inputs holding 0 and p - 1, every launch-time alternative of the plan pinned in turn"""
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     pl, T = _plan(oracle, logm, cls)
     assert pl.log_blowup == 0 and not pl.lde_fused
@@ -105,11 +106,13 @@ def test_lde_sweep(oracle, cls, logm):
     pl.close()
 
 
-def test_lde_three_pass_plan(oracle):
-    """a three-pass decomposition: 4-byte words, p >= 2^30, 2^22 = 8 + 7 + 7 (alternative 1, pinned) and the two-pass default"""
+@pytest.mark.parametrize("p,g", [(3221225473, 5), (2013265921, 31)], ids=["p3221225473", "bb31"])
+def test_lde_three_pass_plan(oracle, p, g):
+    """a three-pass decomposition: 4-byte words, p >= 2^30 (above 2^31, and BabyBear below it: plan.h offers the alternative to every
+    non-lazy 4-byte modulus), 2^22 = 8 + 7 + 7 (alternative 1, pinned) and the two-pass default"""
     import ntt_aie_amd as eng
 
-    p, g, logm = 3221225473, 5, 22
+    logm = 22
     T = oracle.make_table(1, 1 << logm, p, g, 4)
     pl = eng.NTTPlan(logm, p, 4, 0)
     pl.set_twiddles(T)
@@ -128,7 +131,8 @@ def test_lde_three_pass_plan(oracle):
 
 
 @pytest.mark.parametrize("cls,logm", [("gl", 5), ("gl", 10), ("gl", 11), ("gl", 13), ("gl", 16), ("m64", 9), ("m32", 5), ("m32", 10),
-                                      ("m32", 12), ("m32", 14), ("kyber", 7), ("gl", 4), ("m32", 3)])
+                                      ("m32", 12), ("m32", 14), ("kyber", 7), ("gl", 4), ("m32", 3), ("bb31", 12), ("kb31", 14),
+                                      ("top32", 5), ("top32", 10)])
 def test_lde_stays_inside_the_callers_buffers(oracle, cls, logm):
     """memory safety on hardware: d_out carved out of a larger allocation with sentinel words directly before and after, d_in an
     allocation of exactly batch * N words, ragged batches (a last polynomial group that is part empty at the sizes where a
@@ -137,7 +141,7 @@ def test_lde_stays_inside_the_callers_buffers(oracle, cls, logm):
 
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     tdt = torch.int32 if wb == 4 else torch.int64
     pl, T = _plan(oracle, logm, cls)

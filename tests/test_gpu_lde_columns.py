@@ -8,11 +8,12 @@ import functools
 import numpy as np
 import pytest
 
+from test_gpu_columns import ALL_CLASSES, CLASSES, GOLD, STREAM_CLASSES  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-GOLD = 0xFFFFFFFF00000001
-# the four word classes of tests/test_gpu_columns.py; kind-0 tables where kind-1 does not exist
-CLASSES = {"gl": (8, GOLD, 7), "m64": (8, 0xFFFFFFFC00000001, 10), "m32": (4, 998244353, 3), "kyber": (4, 3329, 3)}
+# the seven word classes of tests/test_gpu_columns.py (four, and three more 4-byte moduli for the other two instruction streams);
+# kind-0 tables where kind-1 does not exist
 # (logm, beta, width, in_pitch, out_pitch, count): one pass, several matrices per workgroup, ragged group, two live rows per thread;
 # beta = 4: one live word per thread; 5 + 4; 7 + 6; 8 + 8 with wave-uniform twiddles and an odd source pitch
 LDE_SHAPES = [(4, 3, 17, 18, 19, 19), (5, 4, 3, 3, 5, 3), (9, 1, 33, 40, 48, 2), (13, 3, 33, 48, 33, 1), (16, 2, 100, 101, 128, 1)]
@@ -32,7 +33,7 @@ def _powers(base, exps, p, dt):
 
 
 def _shift(cls, k):
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     return (1, g, p - 1)[k % 3]
 
 
@@ -40,7 +41,7 @@ def _shift(cls, k):
 def _table_cached(logn, cls):
     import oracle_py
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     n = 1 << logn
     T = oracle_py.make_table(1, n, p, g, wb) if (p - 1) % n == 0 else oracle_py.make_roots(n, p, g, wb)
     T.setflags(write=False)
@@ -52,7 +53,7 @@ def _lde_case(cls, logm, beta, width, count, shift):
     """inputs [count][N][width] (holding 0 and p - 1) and the oracle's network on the expanded, scaled columns; computed once, read-only"""
     import oracle_py
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     m, n = 1 << logm, (1 << logm) >> beta
     rng = np.random.default_rng(1000 * logm + 10 * beta + width)
@@ -72,7 +73,7 @@ def _lde_case(cls, logm, beta, width, count, shift):
 def _cinv_case(cls, logn, width, count, shift):
     import oracle_py
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     dt = np.uint32 if wb == 4 else np.uint64
     n = 1 << logn
     rng = np.random.default_rng(2000 * logn + width)
@@ -89,7 +90,7 @@ def _cinv_case(cls, logn, width, count, shift):
 def _plan(logn, cls):
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     pl = eng.NTTPlan(logn, p, wb, 0)
     pl.set_twiddles(np.array(_table_cached(logn, cls)))
     return pl
@@ -119,7 +120,7 @@ class _Guarded:
         return bool((self.big[:self.lead] == self.s).all()) and bool((self.big[end:] == self.s).all()) and bool((self.view[:, :, self.width:] == self.s).all())
 
 
-@pytest.mark.parametrize("cls", sorted(CLASSES))
+@pytest.mark.parametrize("cls", sorted(ALL_CLASSES))
 @pytest.mark.parametrize("shape", LDE_SHAPES, ids=lambda s: "m%d_b%d_w%d_ip%d_op%d_c%d" % s)
 def test_lde_columns_against_the_oracle_with_guard_words(oracle, cls, shape):
     """the guards are intact (the input's padding is non-canonical junk), the input is unchanged, every live word is the oracle's"""
@@ -128,7 +129,7 @@ def test_lde_columns_against_the_oracle_with_guard_words(oracle, cls, shape):
     import ntt_aie_amd as eng
     from ntt_aie_amd import _lib
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logm, beta, width, in_pitch, out_pitch, count = shape
     m = 1 << logm
     shift = _shift(cls, LDE_SHAPES.index(shape))
@@ -147,7 +148,7 @@ def test_lde_columns_against_the_oracle_with_guard_words(oracle, cls, shape):
     pl.close()
 
 
-@pytest.mark.parametrize("cls", sorted(CLASSES))
+@pytest.mark.parametrize("cls", sorted(ALL_CLASSES))
 @pytest.mark.parametrize("shape", CINV_SHAPES, ids=lambda s: "n%d_w%d_p%d_c%d" % s)
 def test_coset_inverse_columns_against_the_oracle_with_guard_words(oracle, cls, shape):
     """out of place and in place, with the same guards"""
@@ -156,7 +157,7 @@ def test_coset_inverse_columns_against_the_oracle_with_guard_words(oracle, cls, 
     import ntt_aie_amd as eng
     from ntt_aie_amd import _lib
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logn, width, pitch, count = shape
     shift = _shift(cls, CINV_SHAPES.index(shape) + 1)
     tdt = torch.int32 if wb == 4 else torch.int64
@@ -178,14 +179,14 @@ def test_coset_inverse_columns_against_the_oracle_with_guard_words(oracle, cls, 
     pl.close()
 
 
-@pytest.mark.parametrize("cls", ["gl", "m32"])
+@pytest.mark.parametrize("cls", ["gl", "m32", "bb31", "top32"])
 def test_round_trip_and_sampled_evaluations(oracle, cls):
     """kind-1 tables, logm 13, beta 3, width 33: coset_inverse_columns(lde_columns(x)) has row j << beta equal to x[j] and every other
     row zero; and for 8 sampled (k, c), lde_columns(x)[k][c] is the column's polynomial -- row j holds coefficient bitrev_N(j) --
     evaluated at shift * w_M^k with Python integers"""
     import ntt_aie_amd as eng
 
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     logm, beta, width = 13, 3, 33
     m, n = 1 << logm, (1 << logm) >> beta
     assert (p - 1) % m == 0
@@ -222,7 +223,7 @@ def test_wrappers_on_strided_views_and_value_errors(oracle):
     import ntt_aie_amd as eng
 
     cls, logm, beta, width, count = "gl", 9, 1, 33, 2
-    wb, p, g = CLASSES[cls]
+    wb, p, g = ALL_CLASSES[cls]
     m, n = 1 << logm, (1 << logm) >> beta
     shift = g
     x, want = _lde_case(cls, logm, beta, width, count, shift)
