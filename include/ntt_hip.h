@@ -327,6 +327,32 @@ int ntt_pointwise_mul(ntt_plan_t plan, const void *d_a, const void *d_b, void *d
 int ntt_polymul_negacyclic(ntt_plan_t plan, void *d_a, void *d_b, void *d_out,
                            size_t batch, void *stream);
 
+/* The same product with operand b PREPARED: b^ = InvU(b), computed once and reused -- a public matrix row, a key-switching key, a
+ * plaintext mask; often ONE polynomial that multiplies every row of a batch.
+ *
+ * ntt_polymul_prepare writes exactly what ntt_inverse(plan, d_b, d_bhat, rows, NTT_LAYOUT_NATURAL, 0, stream) writes, bit for bit
+ * (tests/test_gpu_product_pre.py asserts it).  The prepared form is NOT opaque: [rows][N] canonical words in natural order,
+ * independent of the plan's decomposition alternative and of the batch, valid for every clone of the plan; a caller may produce
+ * it itself.  d_b == d_bhat is allowed.
+ *
+ * ntt_polymul_negacyclic_pre: d_out[r] = Fwd( InvU(d_a[r]) . d_bhat[bhat_rows == 1 ? 0 : r] . N^-1 ).  With bhat_rows == batch this
+ * is word for word what ntt_polymul_negacyclic(plan, a, b, out, batch) returns for bhat = prepare(b); bhat_rows == 1 is the
+ * broadcast: the one row multiplies every row of d_a.  Any other bhat_rows is NTT_E_ARG.  d_a is overwritten (scratch: its inverse
+ * column passes run in place), d_bhat is never written, d_out may alias d_a; d_a or d_out overlapping the bhat_rows * N words of
+ * d_bhat is NTT_E_ARG, as are a null or misaligned pointer and a batch out of range; NTT_E_NOTABLE / NTT_E_NOTINVERTIBLE as for
+ * ntt_polymul_negacyclic; batch == 0 is NTT_OK.  The decomposition is the one ntt_plan_select(plan, batch) names.  Asynchronous on
+ * `stream`, no allocation, no host synchronisation; nothing outside the caller's batch * N words of d_a / d_out and
+ * bhat_rows * N words of d_bhat is accessed.
+ * Where the fused middle pass runs (N >= 2^7 Goldilocks and the general 64-bit modulus, N >= 2^6 4-byte words, a first pass of at
+ * most 12 / 13 stages) the call is a's inverse column passes, ONE middle launch that reads a and b^ and writes the product's first
+ * forward pass, and the forward column passes: at a two-pass size 2 N + 3 N + 2 N = 7 N words of HBM traffic and two transforms'
+ * butterflies, against 9 N words and three transforms for ntt_polymul_negacyclic (a single-pass size: one launch, 3 N words).  That
+ * claim holds ONLY there: every other size runs a's whole unscaled inverse, then the forward transform with b^ folded into the load
+ * of its first pass (per row) or after a separate in-place product launch (broadcast). */
+int ntt_polymul_prepare(ntt_plan_t plan, const void *d_b, void *d_bhat, size_t rows, void *stream);
+int ntt_polymul_negacyclic_pre(ntt_plan_t plan, void *d_a, const void *d_bhat, size_t bhat_rows,
+                               void *d_out, size_t batch, void *stream);
+
 /* Precondition check (blocking, diagnostic): how many of the batch*N words are >= p.  The transforms
  * assume canonical residues, as the reference's vector_modadd / vector_modsub do (src/aie_core.cc:41-62);
  * a non-canonical word gives an unspecified (but memory-safe) result: no kernel reads or writes outside the caller's

@@ -41,7 +41,14 @@ hipError_t launch_product_mid_of(int log_m, const ErasedArgs &a, hipStream_t s);
 extern template hipError_t launch_product_mid_of<FieldGL>(int, const ErasedArgs &, hipStream_t);
 extern template hipError_t launch_product_mid_of<FieldM32>(int, const ErasedArgs &, hipStream_t);
 extern template hipError_t launch_product_mid_of<FieldM64>(int, const ErasedArgs &, hipStream_t);
-hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field
+// ... with operand b prepared (a.in2_prepared: a.in2 is InvU(b), [batch][N] canonical words, or one row when a.in2_broadcast): the
+// second inverse pass is gone.  Kernels of their own (run_product_pass<.., PRE = true>), same unit sizes, kernels_<field>_product_pre.hip
+template <class F>
+hipError_t launch_product_pre_mid_of(int log_m, const ErasedArgs &a, hipStream_t s);
+extern template hipError_t launch_product_pre_mid_of<FieldGL>(int, const ErasedArgs &, hipStream_t);
+extern template hipError_t launch_product_pre_mid_of<FieldM32>(int, const ErasedArgs &, hipStream_t);
+extern template hipError_t launch_product_pre_mid_of<FieldM64>(int, const ErasedArgs &, hipStream_t);
+hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field and a.in2_prepared
 
 #if defined(NTT_EXPERIMENT)
 // Tools-side experiment, NOT part of libntt_hip.so (tools/fused_gl16.hip, libntt_hip_exp.so only):
@@ -56,6 +63,9 @@ hipError_t launch_fused_gl16(const void *in, void *out, const void *tw, size_t b
 // The small kernels (misc_kernels.hip).  Field elements travel as uint64_t whatever the word size.
 // elementwise c = a*b*scale (scale in plain form; scale == 1 skips the second product)
 hipError_t launch_pointwise(const FieldParams &fp, const void *a, const void *b, void *c, size_t count, uint64_t scale, hipStream_t s);
+// in place: buf[r][i] = buf[r][i] * row[i] * scale (plain form all), buf: [batch][2^n] words, row: 2^n words -- the broadcast product of
+// ntt_polymul_negacyclic_pre at the sizes without a fused middle
+hipError_t launch_pointwise_row(const FieldParams &fp, void *buf, const void *row, int n, size_t batch, uint64_t scale, hipStream_t s);
 // device-side table generation (no host upload): T[i] = base^e_kind(i), table form
 hipError_t launch_gen_table(const FieldParams &fp, void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, hipStream_t s);
 // coset vector of ntt_plan_set_coset: s[i] = shift^bitrev_logn(i mod 2^logn), table form, i < len (len = max(2^logn, 4));

@@ -73,6 +73,10 @@ struct ErasedArgs {
     int mat_lde_beta;
     uint32_t mat_src_pitch;
     const void *mat_cinv_u;
+    // product_mid launch of ntt_polymul_negacyclic_pre: in2 is the PREPARED operand InvU(b), natural order, canonical words -- [batch][N],
+    // or ONE row of N words that multiplies every polynomial (in2_broadcast).  Both zero: every other launch
+    int in2_prepared;
+    int in2_broadcast;
 #if defined(NTT_PHASE_STAMPS)
     void *stamps;            // diagnostic build: PassArgs::stamps / stamp_records (ntt_stamps_set)
     uint32_t stamp_records;

@@ -205,6 +205,30 @@ __global__ __launch_bounds__(256) void row_scale_kernel(typename F::W *buf, cons
     for (size_t i = chunks * V + (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) buf[i] = f.mul(buf[i], u[(uint32_t) i & u_mask]);
 }
 
+// The broadcast product of ntt_polymul_negacyclic_pre where no fused middle pass runs: buf[b][i] = buf[b][i] * row[i] * scale in place,
+// plain (canonical) words throughout, one thread per 16-byte chunk, grid-stride.  `row` has EXACTLY row_mask + 1 words: a row shorter
+// than a chunk (N = 2 of 4-byte words) goes word by word, so nothing past the row is read.
+template <class F>
+__global__ __launch_bounds__(256) void pointwise_row_kernel(typename F::W *buf, const typename F::W *row, size_t count, uint32_t row_mask, F f, typename F::W scale) {
+    using W = typename F::W;
+    constexpr int V = 16 / sizeof(W);
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    const size_t chunks = row_mask + 1u >= (uint32_t) V ? count / V : 0, stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t c = (size_t) blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += stride) {
+        const u32x4 xx = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(buf) + c);
+        const Vec<W, V> m = *reinterpret_cast<const Vec<W, V> *>(row + ((uint32_t) (c * V) & row_mask));
+        Vec<W, V> x;
+        __builtin_memcpy(&x, &xx, 16);
+#pragma unroll
+        for (int k = 0; k < V; ++k) x.v[k] = f.mul_plain(f.mul_plain(x.v[k], m.v[k]), scale);
+        u32x4 zz;
+        __builtin_memcpy(&zz, &x, 16);
+        __builtin_nontemporal_store(zz, reinterpret_cast<u32x4 *>(buf) + c);
+    }
+    for (size_t i = chunks * V + (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride)
+        buf[i] = f.mul_plain(f.mul_plain(buf[i], row[(uint32_t) i & row_mask]), scale);
+}
+
 // out[i] = T[i] * c, both in table (Montgomery) form: the scaled stage-0 twiddles of the inverse transform (pass.h: fold_scale)
 template <class F>
 __global__ __launch_bounds__(256) void scale_table_kernel(const typename F::W *T, typename F::W *out, size_t count,
@@ -249,7 +273,9 @@ hipError_t launch_mat_pass(bool inverse, int log_m, const ErasedArgs &a, hipStre
 }
 
 hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s) {
-    return with_field(a.field, [&](auto f) { return launch_product_mid_of<decltype(f)>(log_m, a, s); });
+    return with_field(a.field, [&](auto f) {
+        return a.in2_prepared ? launch_product_pre_mid_of<decltype(f)>(log_m, a, s) : launch_product_mid_of<decltype(f)>(log_m, a, s);
+    });
 }
 
 hipError_t launch_pointwise(const FieldParams &fp, const void *a, const void *b, void *c, size_t count, uint64_t scale, hipStream_t s) {
@@ -259,6 +285,18 @@ hipError_t launch_pointwise(const FieldParams &fp, const void *a, const void *b,
         using W = typename F::W;
         hipLaunchKernelGGL(pointwise_kernel<F>, dim3(grid_for(count / (16 / sizeof(W)))), dim3(256), 0, s, (const W *) a, (const W *) b, (W *) c, count, f,
                            (W) scale, scale != 1 ? 1 : 0);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_pointwise_row(const FieldParams &fp, void *buf, const void *row, int n, size_t batch, uint64_t scale, hipStream_t s) {
+    const size_t count = batch << n;
+    if (count == 0) return hipSuccess;
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        using W = typename F::W;
+        hipLaunchKernelGGL(pointwise_row_kernel<F>, dim3(grid_for((count + 16 / sizeof(W) - 1) / (16 / sizeof(W)))), dim3(256), 0, s, (W *) buf, (const W *) row, count,
+                           (uint32_t) (((size_t) 1 << n) - 1), f, (W) scale);
         return hipGetLastError();
     });
 }

@@ -829,6 +829,47 @@ int ntt_polymul_negacyclic(ntt_plan_t pl, void *d_a, void *d_b, void *d_out, siz
     return run_forward(pl, d_a, d_out, batch, NTT_LAYOUT_NATURAL, s, d_b, pl->ninv_plain, &passes);
 } NTT_GUARD_END
 
+int ntt_polymul_prepare(ntt_plan_t pl, const void *d_b, void *d_bhat, size_t rows, void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_b, d_bhat, rows);
+    if (rc) return rc;
+    if (!pl->has_table) return NTT_E_NOTABLE;
+    if (!pl->has_inv) return NTT_E_NOTINVERTIBLE;
+    if (rows == 0) return NTT_OK;
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    // the prepared form IS the unscaled inverse in natural order: nothing else to it (include/ntt_hip.h)
+    return run_inverse(pl, d_b, d_bhat, rows, NTT_LAYOUT_NATURAL, 0, (hipStream_t) stream);
+} NTT_GUARD_END
+
+int ntt_polymul_negacyclic_pre(ntt_plan_t pl, void *d_a, const void *d_bhat, size_t bhat_rows, void *d_out, size_t batch, void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_a, d_bhat, batch);
+    if (rc) return rc;
+    if (batch && (!d_out || ((uintptr_t) d_out & 15u))) return NTT_E_ARG;
+    if (batch && bhat_rows != 1 && bhat_rows != batch) return NTT_E_ARG;
+    if (!pl->has_table) return NTT_E_NOTABLE;
+    if (!pl->has_inv) return NTT_E_NOTINVERTIBLE;
+    if (batch == 0) return NTT_OK;
+    {  // bhat is read while a and out are written: it lies apart from both (out may be a)
+        const size_t row = table_bytes(pl);
+        const uintptr_t h0 = (uintptr_t) d_bhat, h1 = h0 + bhat_rows * row;
+        for (const void *buf : {(const void *) d_a, (const void *) d_out}) {
+            const uintptr_t b0 = (uintptr_t) buf, b1 = b0 + batch * row;
+            if (b0 < h1 && h0 < b1) return NTT_E_ARG;
+        }
+    }
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    hipStream_t s = (hipStream_t) stream;
+    RoctxRange whole("ntt_polymul_negacyclic_pre");
+    const std::vector<PassDesc> &passes = passes_for(pl, batch);
+    return ntt::seq_polymul_pre(
+        *pl, passes, d_a, d_bhat, bhat_rows, d_out, batch,
+        [&](const ntt::Step &st) {
+            return launch_step(st.family == ntt::STEP_PRODUCT ? "product(pre): fused middle" : st.inverse ? "product(pre): inv pass" : "product(pre): fwd pass", st, s);
+        },
+        [&](void *buf, const void *row) { return (int) ntt::launch_pointwise_row(pl->field, buf, row, pl->logn, batch, pl->ninv_plain, s); });
+} NTT_GUARD_END
+
 int ntt_count_noncanonical(ntt_plan_t pl, const void *d_buf, size_t batch, uint64_t *host_count) NTT_GUARD {
     if (!pl || !host_count) return NTT_E_ARG;
     *host_count = 0;

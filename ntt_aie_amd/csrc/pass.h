@@ -1665,6 +1665,71 @@ NTT_HD void tw_table_read(Ctx<Cfg> &c, const typename Cfg::W *table) {
     for (int k = 0; k < Cfg::E - 1; ++k) c.tw[r][k] = p[k];
 }
 
+// ---- the prepared operand of the product's middle pass (run_product_pass<.., PRE = true>) -----------------------------------
+// Where a thread's E round-0 words of unit iteration `it` live in the prepared operand b^ = InvU(b), [rows][N] canonical words in
+// natural order: `origin` is the wave-uniform word of the workgroup's tile (hi block + polynomial group: uniform_word()), `lane` the
+// thread's own offset; element e is word origin + lane + e.  That is where ci.x[e] sits after the inverse rounds (round 0: a thread
+// owns E consecutive words).  A CONTIG workgroup's tile is TILE_WORDS consecutive words -- consecutive units of one polynomial or,
+// when a polynomial has fewer units than the workgroup, whole consecutive polynomials (LinearGeom) -- so polynomial slot, unit and
+// mid-thread << LOG_E add up to tid << LOG_E (= Ctx::lane_st of the inverse configuration, without a register of its own).
+// bcast: ONE row multiplies every polynomial -- the polynomial-group term of the origin is dropped, and so is the polynomial slot
+// of the lane: its bits n and up.  `words`: the caller's rows * N, which no access may reach.  THE rule of both branches of
+// phase_pre_load: what the host model's sanitizer sweep checks is what the GPU addresses.
+struct PreAddr {
+    size_t origin, words;
+    uint32_t lane;
+};
+template <class Cfg>
+NTT_HD PreAddr pre_addr(const Ctx<Cfg> &c, const PassArgs<Cfg> &a, int it, bool bcast) {
+    static_assert(Cfg::CONTIG && Cfg::INV, "the layout an inverse CONTIG pass ends in");
+    PreAddr r;
+    r.lane = c.tid << Cfg::LOG_E;
+    if (bcast) {
+        r.origin = (size_t) c.bx << (a.log_uh + Cfg::LOG_M);
+        r.lane &= (1u << a.n) - 1u;
+        r.words = (size_t) 1 << a.n;
+    } else {
+        r.origin = uniform_word<Cfg>(c, a, it);
+        r.words = (size_t) a.batch << a.n;
+    }
+    return r;
+}
+// the thread's E words of b^ into pre[] (zeros for a polynomial that does not exist: ragged last group).  Device: 64 bytes per lane
+// as 16-byte loads through a descriptor that ends where the caller's rows * N words end; a wave's loads cover one contiguous span.
+template <class Cfg>
+NTT_HD void phase_pre_load(const Ctx<Cfg> &c, const PassArgs<Cfg> &a, const typename Cfg::W *bhat, int it, bool bcast, typename Cfg::W *pre) {
+    using W = typename Cfg::W;
+    const PreAddr pa = pre_addr<Cfg>(c, a, it, bcast);
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(Cfg::E * sizeof(W) % 16 == 0, "whole 16-byte loads");
+    constexpr int V = 16 / (int) sizeof(W);  // words per load
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    const size_t left = (pa.words - pa.origin) * sizeof(W);  // origin < words: the workgroup's tile starts inside a polynomial that exists
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *) (bhat + pa.origin), 0, left > 0xFFFFFFFFull ? -1 : (int) (uint32_t) left, 0x00020000);
+    const uint32_t voff = pa.lane * (uint32_t) sizeof(W);
+#pragma unroll
+    for (int e = 0; e < Cfg::E; ++e) pre[e] = (W) 0;
+    if (c.active) {
+#pragma unroll
+        for (int k = 0; k < Cfg::E; k += V) {
+            const u32x4 d = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (uint32_t) k * (uint32_t) sizeof(W), NTT_AUX_LD);
+            if constexpr (sizeof(W) == 8) {
+                pre[k] = (W) (((uint64_t) d.y << 32) | d.x);
+                pre[k + 1] = (W) (((uint64_t) d.w << 32) | d.z);
+            } else {
+                pre[k] = (W) d.x;
+                pre[k + 1] = (W) d.y;
+                pre[k + 2] = (W) d.z;
+                pre[k + 3] = (W) d.w;
+            }
+        }
+    }
+#else
+#pragma unroll
+    for (int e = 0; e < Cfg::E; ++e) pre[e] = c.active ? (bhat + pa.origin)[(size_t) pa.lane + (size_t) e] : (W) 0;
+#endif
+}
+
 // ---- fused middle of a negacyclic product ---------------------------------------
 // c = Fwd( InvU(a) . InvU(b) . N^-1 ): the LAST pass of both unscaled inverse transforms and the FIRST pass of the
 // forward transform are CONTIG passes over the same 2^LOG_M-word units, and an inverse CONTIG pass ends in exactly
@@ -1676,8 +1741,12 @@ NTT_HD void tw_table_read(Ctx<Cfg> &c, const typename Cfg::W *table) {
 // Exec: eachI(fn(Ctx<CI>&)), eachF(fn(Ctx<CF>&)), eachIF(fn(Ctx<CI>&, Ctx<CF>&, W *keep, W *pre)), sync(), lds(), pg_base(),
 // tabI() / tabF(): the LDS twiddle tables of the two directions (tw_table_words<C>() words each).
 // M32_MODE: which 4-byte-word instruction stream the butterflies run (see phase_compute); ignored by Goldilocks.
-template <class CI, class CF, class Exec, int M32_MODE = -1>
-NTT_HD void run_product_pass(Exec &ex, const PassArgs<CI> &aa, const PassArgs<CI> &ab, const PassArgs<CF> &af) {
+// PRE: operand b arrives prepared -- ab.in is b^ = InvU(b), [batch][N] canonical words in natural order, or ONE row of N words that
+// multiplies every polynomial (pre_bcast).  Per unit: load a -> load this thread's E words of b^ in the round-0 layout (pre_addr) ->
+// inverse stages of a -> multiply (* N^-1) -> forward stages -> store: no second inverse, no keep / swap, one barrier fewer.
+// b^ is only read.
+template <class CI, class CF, class Exec, int M32_MODE = -1, bool PRE = false>
+NTT_HD void run_product_pass(Exec &ex, const PassArgs<CI> &aa, const PassArgs<CI> &ab, const PassArgs<CF> &af, bool pre_bcast = false) {
     using W = typename CI::W;
     static_assert(CI::CONTIG && CF::CONTIG && CI::INV && !CF::INV, "middle of the product: inverse CONTIG then forward CONTIG");
     static_assert(CI::LOG_M == CF::LOG_M && CI::LOG_E == CF::LOG_E && CI::LOG_NT == CF::LOG_NT && CI::R == CF::R, "same tile");
@@ -1720,49 +1789,83 @@ NTT_HD void run_product_pass(Exec &ex, const PassArgs<CI> &aa, const PassArgs<CI
             phase_load_direct_to<CI, R - 1>(ci, aa, it, ci.x, ci.active);
         });
         prio_up();
-        ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &, W *, W *pre) { phase_load_direct_to<CI, R - 1>(ci, ab, it, pre, ci.active); });
+        if constexpr (PRE) ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &, W *, W *pre) { phase_pre_load<CI>(ci, aa, ab.in, it, pre_bcast, pre); });
+        else ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &, W *, W *pre) { phase_load_direct_to<CI, R - 1>(ci, ab, it, pre, ci.active); });
         prio_down();
         inverse_unit(aa, tile);
-        ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &, W *keep, W *pre) {
-#pragma unroll
-            for (int e = 0; e < CI::E; ++e) {
-                keep[e] = ci.x[e];
-                ci.x[e] = pre[e];
-            }
-        });
-        ex.sync(WL{});  // every wave has read its round-0 words: the tile may be rewritten
-        inverse_unit(ab, tile);
-        // word-by-word product * N^-1.  Both factors are arbitrary 64-bit representatives (the inverse butterflies
-        // carry lazy sums): the first product is then a correct 64-bit representative, the second one (by the
-        // canonical constant pw_scale) is canonical -- no canonicalisation pass in between.
-        ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &cf, W *keep, W *) {
+        if constexpr (PRE) {
+            // b^ is canonical, ci.x carries the lazy sums of the inverse butterflies: the first product (multiplier b^ < p, as
+            // m64_mul2 asks of its second argument) is a correct representative, the second one (by the canonical pw_scale)
+            // canonical.  The same paired streams as below, on ci.x instead of keep.
+            ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &cf, W *, W *pre) {
 #if defined(__HIP_DEVICE_COMPILE__)
-            if constexpr (std::is_same<typename CI::F, FieldGL>::value && CI::E >= 2 && CI::LOG_E < 4) {
-                static_for<0, CI::E / 2>([&](auto pp) {
-                    constexpr int e = 2 * decltype(pp)::value;
-                    gl_mul2_v_lo(keep[e], ci.x[e], keep[e + 1], ci.x[e + 1]);
-                    gl_mul2_v_lo(keep[e], af.pw_scale, keep[e + 1], af.pw_scale);
-                    cf.x[e] = keep[e];
-                    cf.x[e + 1] = keep[e + 1];
-                });
-                return;
-            }
-            if constexpr (std::is_same<typename CI::F, FieldM64>::value && CI::E >= 2 && CI::LOG_E < 4) {
-                // (both factors canonical here: the general modulus keeps canonical sums; the multiplier of m64_mul2 must be < p)
-                static_for<0, CI::E / 2>([&](auto pp) {
-                    constexpr int e = 2 * decltype(pp)::value;
-                    m64_mul2_v_lo(keep[e], ci.x[e], keep[e + 1], ci.x[e + 1], af.field.p, af.field.pinv);
-                    m64_mul2_s_lo(keep[e], af.pw_scale, keep[e + 1], af.pw_scale, af.field.p, af.field.pinv);
-                    cf.x[e] = keep[e];
-                    cf.x[e + 1] = keep[e + 1];
-                });
-                return;
-            }
+                if constexpr (std::is_same<typename CI::F, FieldGL>::value && CI::E >= 2 && CI::LOG_E < 4) {
+                    static_for<0, CI::E / 2>([&](auto pp) {
+                        constexpr int e = 2 * decltype(pp)::value;
+                        gl_mul2_v_lo(ci.x[e], pre[e], ci.x[e + 1], pre[e + 1]);
+                        gl_mul2_v_lo(ci.x[e], af.pw_scale, ci.x[e + 1], af.pw_scale);
+                        cf.x[e] = ci.x[e];
+                        cf.x[e + 1] = ci.x[e + 1];
+                    });
+                    return;
+                }
+                if constexpr (std::is_same<typename CI::F, FieldM64>::value && CI::E >= 2 && CI::LOG_E < 4) {
+                    static_for<0, CI::E / 2>([&](auto pp) {
+                        constexpr int e = 2 * decltype(pp)::value;
+                        m64_mul2_v_lo(ci.x[e], pre[e], ci.x[e + 1], pre[e + 1], af.field.p, af.field.pinv);
+                        m64_mul2_s_lo(ci.x[e], af.pw_scale, ci.x[e + 1], af.pw_scale, af.field.p, af.field.pinv);
+                        cf.x[e] = ci.x[e];
+                        cf.x[e + 1] = ci.x[e + 1];
+                    });
+                    return;
+                }
 #endif
 #pragma unroll
-            for (int e = 0; e < CI::E; ++e) cf.x[e] = af.field.mul(af.field.mul(keep[e], ci.x[e]), af.pw_scale);
-        });
+                for (int e = 0; e < CI::E; ++e) cf.x[e] = af.field.mul(af.field.mul(ci.x[e], pre[e]), af.pw_scale);
+            });
+        } else {
+            ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &, W *keep, W *pre) {
+#pragma unroll
+                for (int e = 0; e < CI::E; ++e) {
+                    keep[e] = ci.x[e];
+                    ci.x[e] = pre[e];
+                }
+            });
+            ex.sync(WL{});  // every wave has read its round-0 words: the tile may be rewritten
+            inverse_unit(ab, tile);
+            // word-by-word product * N^-1.  Both factors are arbitrary 64-bit representatives (the inverse butterflies
+            // carry lazy sums): the first product is then a correct 64-bit representative, the second one (by the
+            // canonical constant pw_scale) is canonical -- no canonicalisation pass in between.
+            ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &cf, W *keep, W *) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                if constexpr (std::is_same<typename CI::F, FieldGL>::value && CI::E >= 2 && CI::LOG_E < 4) {
+                    static_for<0, CI::E / 2>([&](auto pp) {
+                        constexpr int e = 2 * decltype(pp)::value;
+                        gl_mul2_v_lo(keep[e], ci.x[e], keep[e + 1], ci.x[e + 1]);
+                        gl_mul2_v_lo(keep[e], af.pw_scale, keep[e + 1], af.pw_scale);
+                        cf.x[e] = keep[e];
+                        cf.x[e + 1] = keep[e + 1];
+                    });
+                    return;
+                }
+                if constexpr (std::is_same<typename CI::F, FieldM64>::value && CI::E >= 2 && CI::LOG_E < 4) {
+                    // (both factors canonical here: the general modulus keeps canonical sums; the multiplier of m64_mul2 must be < p)
+                    static_for<0, CI::E / 2>([&](auto pp) {
+                        constexpr int e = 2 * decltype(pp)::value;
+                        m64_mul2_v_lo(keep[e], ci.x[e], keep[e + 1], ci.x[e + 1], af.field.p, af.field.pinv);
+                        m64_mul2_s_lo(keep[e], af.pw_scale, keep[e + 1], af.pw_scale, af.field.p, af.field.pinv);
+                        cf.x[e] = keep[e];
+                        cf.x[e + 1] = keep[e + 1];
+                    });
+                    return;
+                }
+#endif
+#pragma unroll
+                for (int e = 0; e < CI::E; ++e) cf.x[e] = af.field.mul(af.field.mul(keep[e], ci.x[e]), af.pw_scale);
+            });
+        }
         // no barrier here: the forward rounds first WRITE the round-0 positions, which this thread itself read last
+        // (PRE: the same -- the only inverse_unit of the iteration ends in phase_lds_read<CI, 0>, and the words of b^ never touch LDS)
         static_for<0, R>([&](auto kk) {
             constexpr int r = decltype(kk)::value;
             if constexpr (!CF::preload(r) && (!NTT_PRODUCT_TW_EARLY || r == 0))
@@ -1778,6 +1881,7 @@ NTT_HD void run_product_pass(Exec &ex, const PassArgs<CI> &aa, const PassArgs<CI
         ex.eachF([&](Ctx<CF> &c) { phase_canon<CF>(c, af); });
         ex.eachF([&](Ctx<CF> &c) { phase_store_direct<CF, R - 1>(c, af, it); });
         // ... and none here: the next unit's first LDS write goes to the round R-1 positions this thread read last
+        // (PRE: the forward rounds end in phase_lds_read<CF, R - 1> as before, and the next unit begins with inverse round R - 1)
     }
 }
 

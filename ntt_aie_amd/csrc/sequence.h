@@ -295,4 +295,37 @@ int seq_polymul_fused(const PlanFacts &pf, const std::vector<host::PassDesc> &pa
     return seq_passes(pf, passes, 1, passes.size(), false, out, out, batch, LAYOUT_NATURAL, [](ErasedArgs &, size_t) {}, emit);
 }
 
+// ntt_polymul_negacyclic_pre: operand b arrives prepared, bhat = InvU(b) in natural order, canonical words -- [batch][N] (bhat_rows ==
+// batch) or ONE row that multiplies every polynomial (bhat_rows == 1); bhat is never written.
+// Where polymul_fused(): the inverse column passes of a alone, over `batch` rows, then ONE launch that runs the last inverse pass of a,
+// the product with the thread's words of bhat * N^-1 and the first forward pass per resident unit (in2 = bhat, in2_prepared, in2_broadcast),
+// then the forward column passes in place on `out`.  A single-pass size is the middle step alone.
+// Everywhere else: the unscaled inverse of a in place, then the forward transform with the per-row operand folded into its first pass
+// (seq_forward's in2), or -- the broadcast -- row_mul(a, bhat), which multiplies every row of a by bhat * N^-1 in place (a launch of its
+// own, kernels.h: launch_pointwise_row), and the plain forward transform.
+template <class Emit, class RowMul>
+int seq_polymul_pre(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, void *a, const void *bhat, size_t bhat_rows, void *out, size_t batch, Emit &&emit,
+                    RowMul &&row_mul) {
+    const bool bcast = bhat_rows != batch;  // (batch == 1: the two cases are one, and the per-row addressing serves it)
+    if (!polymul_fused(pf, passes, batch)) {
+        if (const int rc = seq_inverse(pf, passes, a, a, batch, LAYOUT_NATURAL, 0, emit)) return rc;
+        if (!bcast) return seq_forward(pf, passes, a, out, batch, LAYOUT_NATURAL, bhat, pf.ninv_plain, nullptr, emit);
+        if (const int rc = row_mul(a, bhat)) return rc;
+        return seq_forward(pf, passes, a, out, batch, LAYOUT_NATURAL, nullptr, 1, nullptr, emit);
+    }
+    for (size_t i = passes.size(); i-- > 1;)
+        if (const int rc = emit(pass_step(pf, passes[i], (int) i, true, a, a, batch, LAYOUT_NATURAL))) return rc;
+    const host::PassDesc &first = passes.front();
+    Step mid{STEP_PRODUCT, false, true, first.log_m, 0, step_args(pf, first, a, out, batch)};
+    mid.args.in2 = bhat;
+    mid.args.in2_prepared = 1;
+    mid.args.in2_broadcast = bcast ? 1 : 0;
+    mid.args.tw = pf.tw_inv;
+    mid.args.tw2 = pf.tw_fwd;
+    mid.args.layout = LAYOUT_NATURAL;
+    mid.args.pw_scale = pw_scale_form(pf, pf.ninv_plain);
+    if (const int rc = emit(mid)) return rc;
+    return seq_passes(pf, passes, 1, passes.size(), false, out, out, batch, LAYOUT_NATURAL, [](ErasedArgs &, size_t) {}, emit);
+}
+
 }  // namespace ntt

@@ -407,6 +407,35 @@ class NTTPlan:
                                                 self._stream(stream)), "ntt_polymul_negacyclic")
         return out
 
+    def polymul_prepare(self, b: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """The transform-domain form polymul_negacyclic_pre() takes as its fixed operand (ntt_polymul_prepare): exactly
+        inverse(b, scale=False) -- [rows][N] canonical words in natural order, valid for every clone of the plan and every batch.
+        `out` may be `b`."""
+        out = self._out_like(b, stream) if out is None else out
+        rows = self._batch(b, out)
+        check(_lib.lib().ntt_polymul_prepare(self._h, b.data_ptr(), out.data_ptr(), rows, self._stream(stream)), "ntt_polymul_prepare")
+        return out
+
+    def polymul_negacyclic_pre(self, a: torch.Tensor, bhat: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """c = a*b mod (x^N + 1, p) with b given prepared, bhat = polymul_prepare(b) (ntt_polymul_negacyclic_pre); needs a kind-2
+        table.  bhat of shape [N] or [1, N] multiplies EVERY row of a (the broadcast); [batch, N] is one operand per row.  a is
+        overwritten (scratch; `out` defaults to it), bhat is only read and must not overlap a or out."""
+        out = a if out is None else out
+        n = self._batch(a, out)
+        if not bhat.is_cuda or bhat.device.index != self.device:
+            raise ValueError("buffer is not on cuda:%d" % self.device)
+        if not bhat.is_contiguous() or bhat.element_size() != self.word_bytes:
+            raise ValueError("buffer must be contiguous with %d-byte words" % self.word_bytes)
+        if bhat.numel() == self.n and bhat.dim() in (1, 2):
+            rows = 1
+        elif bhat.numel() == a.numel() and bhat.dim() >= 2:
+            rows = n
+        else:
+            raise ValueError("bhat must be [N] or [1, N] (broadcast) or have one row of N words per row of a")
+        check(_lib.lib().ntt_polymul_negacyclic_pre(self._h, a.data_ptr(), bhat.data_ptr(), rows, out.data_ptr(), n,
+                                                    self._stream(stream)), "ntt_polymul_negacyclic_pre")
+        return out
+
     def count_noncanonical(self, buf: torch.Tensor) -> int:
         """How many words of `buf` are >= p (the transforms require canonical residues)."""
         b = self._batch(buf)
