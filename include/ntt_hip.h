@@ -353,6 +353,34 @@ int ntt_polymul_prepare(ntt_plan_t plan, const void *d_b, void *d_bhat, size_t r
 int ntt_polymul_negacyclic_pre(ntt_plan_t plan, void *d_a, const void *d_bhat, size_t bhat_rows,
                                void *d_out, size_t batch, void *stream);
 
+/* The negacyclic INNER product with prepared operands -- an RLWE key switch sum_k digit_k(a) * ksk_k, a module-LWE row sum_k A[i][k] * s[k], a
+ * relinearisation -- summed inside the middle pass:
+ *   d_out[r] = Fwd( N^-1 . sum_{k < terms} InvU(d_a[k][r]) . d_bhat[k][bhat_rows == 1 ? 0 : r] ),  r < batch,  kind-2 table loaded.
+ * d_a is [terms][batch][N] words, contiguous; it is scratch and is overwritten (the inverse column passes run in place, and the sizes
+ * without a fused middle leave the sum in term 0's block).  d_bhat is [terms][bhat_rows][N] canonical words in natural order, row (k, .)
+ * exactly what ntt_polymul_prepare writes; it is never written.  bhat_rows is batch, or 1: ONE polynomial per term multiplies every row
+ * (the key-switching case).  d_out is [batch][N].
+ * Values: with terms == 1 the words are ntt_polymul_negacyclic_pre's, bit for bit; for every `terms` they are the sum mod p of the
+ * `terms` separate ntt_polymul_negacyclic_pre results (all canonical, so the equality is exact), by linearity of Fwd -- ONE forward
+ * transform runs, whatever `terms`, and terms + 1 modular products per word instead of 2 * terms.
+ * d_out may be d_a (term 0's block) or lie apart from all terms * batch * N words of d_a; any other overlap with d_a is NTT_E_ARG, as is any
+ * overlap of d_a or d_out with the terms * bhat_rows * N words of d_bhat, a null or misaligned pointer, bhat_rows other than 1 or batch,
+ * terms == 0 with batch > 0, and terms * batch > 2^31 - 1.  NTT_E_NOTABLE / NTT_E_NOTINVERTIBLE as for ntt_polymul_negacyclic_pre;
+ * batch == 0 is NTT_OK whatever the other arguments.  The decomposition is the one ntt_plan_select(plan, batch) names -- selected by
+ * `batch`, not by terms * batch -- and a pinned policy is honoured.  Asynchronous on `stream`, no allocation, no host synchronisation;
+ * nothing outside the caller's terms * batch * N words of d_a, terms * bhat_rows * N words of d_bhat and batch * N words of d_out is accessed.
+ * Where the fused middle pass runs (the sizes named at ntt_polymul_negacyclic_pre) the call is a's inverse column passes as one launch
+ * each over terms * batch rows, ONE middle launch that reads every term's unit of a and of b^ and writes the first forward pass of the
+ * sum, and the forward column passes over batch rows.  Derived (not measured with counters) HBM traffic at a two-pass size, K = terms:
+ * 2 K N + (2 K + 1) N + 2 N = (4 K + 3) N words, against 7 K N for K calls of ntt_polymul_negacyclic_pre plus 3 (K - 1) N for the sums
+ * a caller adds; a single-pass size: one launch, (2 K + 1) N words.  (A broadcast reads the K N words of b^ once per workgroup, from
+ * cache for all but the first.)  That derivation holds ONLY there: every other size runs the whole unscaled inverse over terms * batch
+ * rows, one small launch that sums the products into term 0's block, and the plain forward transform -- still one forward transform,
+ * but a pass more each way: (6 K + 5) N words at a two-pass size.  Besides the sizes named there, that is the path of the general 64-bit
+ * modulus where the first pass has 10 stages and of 4-byte words where it has 13: the summed middle has no kernel for those two units. */
+int ntt_polymul_dot_pre(ntt_plan_t plan, void *d_a, const void *d_bhat, size_t bhat_rows, size_t terms,
+                        void *d_out, size_t batch, void *stream);
+
 /* Precondition check (blocking, diagnostic): how many of the batch*N words are >= p.  The transforms
  * assume canonical residues, as the reference's vector_modadd / vector_modsub do (src/aie_core.cc:41-62);
  * a non-canonical word gives an unspecified (but memory-safe) result: no kernel reads or writes outside the caller's

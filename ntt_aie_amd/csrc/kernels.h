@@ -48,7 +48,15 @@ hipError_t launch_product_pre_mid_of(int log_m, const ErasedArgs &a, hipStream_t
 extern template hipError_t launch_product_pre_mid_of<FieldGL>(int, const ErasedArgs &, hipStream_t);
 extern template hipError_t launch_product_pre_mid_of<FieldM32>(int, const ErasedArgs &, hipStream_t);
 extern template hipError_t launch_product_pre_mid_of<FieldM64>(int, const ErasedArgs &, hipStream_t);
-hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field and a.in2_prepared
+// ... summed over a.dot_terms terms (ntt_polymul_dot_pre): per unit, for every term the inverse pass of its block of a and the product
+// with its block of the prepared operand, accumulated in registers; ONE scaling by pw_scale, forward pass -> a.out.  Kernels of their
+// own (run_product_dot_pass), same unit sizes, kernels_<field>_product_dot.hip
+template <class F>
+hipError_t launch_product_dot_mid_of(int log_m, const ErasedArgs &a, hipStream_t s);
+extern template hipError_t launch_product_dot_mid_of<FieldGL>(int, const ErasedArgs &, hipStream_t);
+extern template hipError_t launch_product_dot_mid_of<FieldM32>(int, const ErasedArgs &, hipStream_t);
+extern template hipError_t launch_product_dot_mid_of<FieldM64>(int, const ErasedArgs &, hipStream_t);
+hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field, a.in2_prepared and a.dot_terms
 
 #if defined(NTT_EXPERIMENT)
 // Tools-side experiment, NOT part of libntt_hip.so (tools/fused_gl16.hip, libntt_hip_exp.so only):
@@ -66,6 +74,10 @@ hipError_t launch_pointwise(const FieldParams &fp, const void *a, const void *b,
 // in place: buf[r][i] = buf[r][i] * row[i] * scale (plain form all), buf: [batch][2^n] words, row: 2^n words -- the broadcast product of
 // ntt_polymul_negacyclic_pre at the sizes without a fused middle
 hipError_t launch_pointwise_row(const FieldParams &fp, void *buf, const void *row, int n, size_t batch, uint64_t scale, hipStream_t s);
+// in place on term 0: a[0][r][i] = scale2 * sum_k a[k][r][i] * bhat[k][bhat_rows == 1 ? 0 : r][i] / R^2 -- plain words in and out when scale2
+// is the scale times R^2 in table form (sequence.h: pw_scale_form); a: [terms][batch][2^n] words, bhat: [terms][bhat_rows][2^n] words, read
+// only.  The sum of ntt_polymul_dot_pre at the sizes without a fused middle
+hipError_t launch_dot_rows(const FieldParams &fp, void *a, const void *bhat, int n, size_t batch, size_t bhat_rows, size_t terms, uint64_t scale2, hipStream_t s);
 // device-side table generation (no host upload): T[i] = base^e_kind(i), table form
 hipError_t launch_gen_table(const FieldParams &fp, void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, hipStream_t s);
 // coset vector of ntt_plan_set_coset: s[i] = shift^bitrev_logn(i mod 2^logn), table form, i < len (len = max(2^logn, 4));

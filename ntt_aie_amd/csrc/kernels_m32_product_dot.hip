@@ -1,0 +1,5 @@
+// kernels_m32_product_dot.hip -- the fused middle pass of the negacyclic inner product with prepared operands (pass.h: run_product_dot_pass;
+// ntt_polymul_dot_pre), 4-byte words: every unit size kernels_m32_product.hip has.  A translation unit of its own: the build's parallelism.
+#define NTT_FIELD FieldM32
+#define NTT_PRODUCT_DOT 1
+#include "product_kernel.inc"

@@ -77,6 +77,12 @@ struct ErasedArgs {
     // or ONE row of N words that multiplies every polynomial (in2_broadcast).  Both zero: every other launch
     int in2_prepared;
     int in2_broadcast;
+    // product_mid launch of ntt_polymul_dot_pre: the prepared middle summed over dot_terms terms (0: every other launch).  Term k reads its
+    // unit of operand a at in + k * dot_in_stride words and its prepared words at in2 + k * dot_in2_stride words (in2_prepared set,
+    // in2_broadcast as above, per term); `batch` is the rows of ONE term
+    int dot_terms;
+    uint64_t dot_in_stride;
+    uint64_t dot_in2_stride;
 #if defined(NTT_PHASE_STAMPS)
     void *stamps;            // diagnostic build: PassArgs::stamps / stamp_records (ntt_stamps_set)
     uint32_t stamp_records;
@@ -322,6 +328,36 @@ inline bool product_mid_fits(const FieldParams &fp, int log_m, int n, uint32_t b
         product_dispatch<decltype(f)>(log_m, [&](auto tag) { fits = product_geometry<typename decltype(tag)::Cfg>(n, batch, target_wgs).grid_y <= 65535u; });
         return fits;
     });
+}
+
+// The summed middle of ntt_polymul_dot_pre (pass.h: run_product_dot_pass) has a kernel for every unit size of product_dispatch but two:
+// the general 64-bit modulus at 2^10 and 4-byte words at 2^13.  Their prepared twins sit at 125 and 128 VGPRs, and the term loop's
+// extra live state tips the register allocator into 20 bytes of scratch under the same 128-VGPR bound; a kernel
+// is not shipped with spills, so those two sizes take the path of the sizes without a fused middle.
+template <class F>
+constexpr bool product_dot_unit(int log_m) {
+    return !(std::is_same<F, FieldM64>::value && log_m == 10) && !(std::is_same<F, FieldM32>::value && log_m == 13);
+}
+template <class F, class Fn>
+bool product_dot_dispatch(int log_m, Fn &&fn) {
+    bool found = false;
+    product_dispatch<F>(log_m, [&](auto tag) {
+        if constexpr (product_dot_unit<F>(decltype(tag)::Cfg::CI::LOG_M)) {
+            fn(tag);
+            found = true;
+        }
+    });
+    return found;
+}
+// ... and the sizes ntt_polymul_dot_pre takes it at: those of product_mid_used that have such a kernel
+inline bool product_dot_used(const FieldParams &fp, int log_m) {
+    return product_mid_used(fp, log_m) && with_field(fp, [&](auto f) { return product_dot_unit<decltype(f)>(log_m); });
+}
+
+// what a launch of the summed middle (run_product_dot_pass) must carry: shared by the GPU launcher and the host model
+inline bool product_dot_args_ok(const ErasedArgs &e) {
+    const uint64_t row = (uint64_t) 1 << e.n;
+    return e.dot_terms > 0 && e.in2_prepared && e.dot_in_stride == (uint64_t) e.batch * row && e.dot_in2_stride == (e.in2_broadcast ? row : (uint64_t) e.batch * row);
 }
 
 // one leg of the product launch: the inverse pass of an operand (in, no out) or the forward pass of the product (out, no in)

@@ -229,6 +229,44 @@ __global__ __launch_bounds__(256) void pointwise_row_kernel(typename F::W *buf, 
         buf[i] = f.mul_plain(f.mul_plain(buf[i], row[(uint32_t) i & row_mask]), scale);
 }
 
+// The sum of ntt_polymul_dot_pre where no fused middle pass runs: a[0][r][i] = scale2 * sum_k a[k][r][i] * bhat[k][r | 0][i] / R^2 in place on
+// term 0 (R = 2^32 or 2^64: scale2 = N^-1 * R^2 gives plain words from plain words), one thread per 16-byte chunk of the [batch][N] block,
+// grid-stride; term k of a lies a_stride words on, of bhat b_stride words.  mul(x, m) is canonical for canonical m, so the running sum
+// is canonical and add() exact; terms + 1 products per word.  bcast: a term of bhat has EXACTLY row_mask + 1 words -- a row shorter
+// than a chunk (N = 2 of 4-byte words) goes word by word, so nothing past it is read.  bhat is only read.
+template <class F>
+__global__ __launch_bounds__(256) void dot_rows_kernel(typename F::W *a, const typename F::W *bhat, size_t count, uint32_t row_mask, int bcast, uint32_t terms,
+                                                       size_t a_stride, size_t b_stride, F f, typename F::W scale2) {
+    using W = typename F::W;
+    constexpr int V = 16 / sizeof(W);
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    const size_t chunks = row_mask + 1u >= (uint32_t) V ? count / V : 0, stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t c = (size_t) blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += stride) {
+        const size_t w = bcast ? (size_t) ((uint32_t) (c * V) & row_mask) : c * V;  // first word of the chunk inside a term of bhat
+        Vec<W, V> acc;
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc.v[k] = (W) 0;
+        for (uint32_t t = 0; t < terms; ++t) {
+            const u32x4 xx = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(a + (size_t) t * a_stride) + c);
+            const Vec<W, V> m = *reinterpret_cast<const Vec<W, V> *>(bhat + (size_t) t * b_stride + w);
+            Vec<W, V> x;
+            __builtin_memcpy(&x, &xx, 16);
+#pragma unroll
+            for (int k = 0; k < V; ++k) acc.v[k] = f.add(acc.v[k], f.mul(x.v[k], m.v[k]));
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc.v[k] = f.mul(acc.v[k], scale2);
+        u32x4 zz;
+        __builtin_memcpy(&zz, &acc, 16);
+        __builtin_nontemporal_store(zz, reinterpret_cast<u32x4 *>(a) + c);
+    }
+    for (size_t i = chunks * V + (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        W acc = (W) 0;
+        for (uint32_t t = 0; t < terms; ++t) acc = f.add(acc, f.mul(a[(size_t) t * a_stride + i], bhat[(size_t) t * b_stride + (bcast ? (size_t) ((uint32_t) i & row_mask) : i)]));
+        a[i] = f.mul(acc, scale2);
+    }
+}
+
 // out[i] = T[i] * c, both in table (Montgomery) form: the scaled stage-0 twiddles of the inverse transform (pass.h: fold_scale)
 template <class F>
 __global__ __launch_bounds__(256) void scale_table_kernel(const typename F::W *T, typename F::W *out, size_t count,
@@ -274,6 +312,7 @@ hipError_t launch_mat_pass(bool inverse, int log_m, const ErasedArgs &a, hipStre
 
 hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s) {
     return with_field(a.field, [&](auto f) {
+        if (a.dot_terms != 0) return launch_product_dot_mid_of<decltype(f)>(log_m, a, s);
         return a.in2_prepared ? launch_product_pre_mid_of<decltype(f)>(log_m, a, s) : launch_product_mid_of<decltype(f)>(log_m, a, s);
     });
 }
@@ -297,6 +336,18 @@ hipError_t launch_pointwise_row(const FieldParams &fp, void *buf, const void *ro
         using W = typename F::W;
         hipLaunchKernelGGL(pointwise_row_kernel<F>, dim3(grid_for((count + 16 / sizeof(W) - 1) / (16 / sizeof(W)))), dim3(256), 0, s, (W *) buf, (const W *) row, count,
                            (uint32_t) (((size_t) 1 << n) - 1), f, (W) scale);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_dot_rows(const FieldParams &fp, void *a, const void *bhat, int n, size_t batch, size_t bhat_rows, size_t terms, uint64_t scale2, hipStream_t s) {
+    const size_t count = batch << n;
+    if (count == 0 || terms == 0) return hipSuccess;
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        using W = typename F::W;
+        hipLaunchKernelGGL(dot_rows_kernel<F>, dim3(grid_for((count + 16 / sizeof(W) - 1) / (16 / sizeof(W)))), dim3(256), 0, s, (W *) a, (const W *) bhat, count,
+                           (uint32_t) (((size_t) 1 << n) - 1), bhat_rows != batch ? 1 : 0, (uint32_t) terms, count, bhat_rows << n, f, (W) scale2);
         return hipGetLastError();
     });
 }

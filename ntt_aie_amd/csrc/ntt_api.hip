@@ -870,6 +870,40 @@ int ntt_polymul_negacyclic_pre(ntt_plan_t pl, void *d_a, const void *d_bhat, siz
         [&](void *buf, const void *row) { return (int) ntt::launch_pointwise_row(pl->field, buf, row, pl->logn, batch, pl->ninv_plain, s); });
 } NTT_GUARD_END
 
+int ntt_polymul_dot_pre(ntt_plan_t pl, void *d_a, const void *d_bhat, size_t bhat_rows, size_t terms, void *d_out, size_t batch, void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_a, d_bhat, batch);
+    if (rc) return rc;
+    if (batch && (!d_out || ((uintptr_t) d_out & 15u))) return NTT_E_ARG;
+    if (batch && bhat_rows != 1 && bhat_rows != batch) return NTT_E_ARG;
+    if (batch && (terms == 0 || terms > 0x7FFFFFFFull / batch)) return NTT_E_ARG;  // the inverse passes run over terms * batch rows
+    if (!pl->has_table) return NTT_E_NOTABLE;
+    if (!pl->has_inv) return NTT_E_NOTINVERTIBLE;
+    if (batch == 0) return NTT_OK;
+    {
+        const size_t row = table_bytes(pl);
+        const uintptr_t a0 = (uintptr_t) d_a, a1 = a0 + terms * batch * row, o0 = (uintptr_t) d_out, o1 = o0 + batch * row;
+        const uintptr_t h0 = (uintptr_t) d_bhat, h1 = h0 + terms * bhat_rows * row;
+        // out is term 0's block of a or lies apart from all of a: every other overlap is overwritten while terms are still to be read
+        if (o0 != a0 && o0 < a1 && a0 < o1) return NTT_E_ARG;
+        // bhat is read while a and out are written: it lies apart from both
+        if ((a0 < h1 && h0 < a1) || (o0 < h1 && h0 < o1)) return NTT_E_ARG;
+    }
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    hipStream_t s = (hipStream_t) stream;
+    RoctxRange whole("ntt_polymul_dot_pre");
+    const std::vector<PassDesc> &passes = passes_for(pl, batch);  // by batch, not by terms * batch (include/ntt_hip.h)
+    return ntt::seq_polymul_dot(
+        *pl, passes, d_a, d_bhat, bhat_rows, terms, d_out, batch,
+        [&](const ntt::Step &st) {
+            return launch_step(st.family == ntt::STEP_PRODUCT ? "product(dot): fused middle" : st.inverse ? "product(dot): inv pass" : "product(dot): fwd pass", st, s);
+        },
+        [&](void *buf, const void *hat) {
+            RoctxRange sum("product(dot): row sum");
+            return (int) ntt::launch_dot_rows(pl->field, buf, hat, pl->logn, batch, bhat_rows, terms, ntt::pw_scale_form(*pl, pl->ninv_plain), s);
+        });
+} NTT_GUARD_END
+
 int ntt_count_noncanonical(ntt_plan_t pl, const void *d_buf, size_t batch, uint64_t *host_count) NTT_GUARD {
     if (!pl || !host_count) return NTT_E_ARG;
     *host_count = 0;

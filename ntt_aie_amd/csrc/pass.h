@@ -1885,6 +1885,131 @@ NTT_HD void run_product_pass(Exec &ex, const PassArgs<CI> &aa, const PassArgs<CI
     }
 }
 
+// ---- inner product with prepared operands (ntt_polymul_dot_pre): the middle pass summed over terms ---------------------------
+// acc[e] += x[e] . b^[e] for the thread's E round-0 words of unit iteration `it` of ONE term: `bhat` is that term's block of the
+// prepared operand, and pre_addr is the address rule -- origin, lane and the word count no access may reach are the prepared
+// kernel's, per term.  Device: the same 16-byte loads through a descriptor that ends where the term's rows * N words end, each
+// consumed as it arrives, so that no E-word copy of b^ is live beside x and acc.  Inactive lanes (ragged last group) load nothing.
+// b^ is canonical and x any representative the inverse butterflies leave: field.mul(x, b^) is CANONICAL for all three fields
+// (field.h: hi - mh lies in (-p, p) and is corrected once), so acc stays canonical and field.add sees a true sum below 2p.
+template <class Cfg>
+NTT_HD void phase_pre_mac(const Ctx<Cfg> &c, const PassArgs<Cfg> &a, const typename Cfg::W *bhat, int it, bool bcast, typename Cfg::W *acc) {
+    const PreAddr pa = pre_addr<Cfg>(c, a, it, bcast);
+    if (!c.active) return;
+#if defined(__HIP_DEVICE_COMPILE__)
+    using W = typename Cfg::W;
+    static_assert(Cfg::E * sizeof(W) % 16 == 0, "whole 16-byte loads");
+    constexpr int V = 16 / (int) sizeof(W);  // words per load
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    const size_t left = (pa.words - pa.origin) * sizeof(W);  // origin < words, as in phase_pre_load
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *) (bhat + pa.origin), 0, left > 0xFFFFFFFFull ? -1 : (int) (uint32_t) left, 0x00020000);
+    const uint32_t voff = pa.lane * (uint32_t) sizeof(W);
+    // two loads in flight at most: the next 16 bytes are requested, the current ones consumed, and nothing crosses the fence between
+    // two steps -- left to itself the scheduler hoists all E words above the first product and the kernel spills
+    u32x4 d = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0u, NTT_AUX_LD);
+#pragma unroll
+    for (int k = 0; k < Cfg::E; k += V) {
+        u32x4 nx = d;
+        if (k + V < Cfg::E) nx = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (uint32_t) (k + V) * (uint32_t) sizeof(W), NTT_AUX_LD);
+        if constexpr (sizeof(W) == 8) {
+            acc[k] = a.field.add(acc[k], a.field.mul(c.x[k], (W) (((uint64_t) d.y << 32) | d.x)));
+            acc[k + 1] = a.field.add(acc[k + 1], a.field.mul(c.x[k + 1], (W) (((uint64_t) d.w << 32) | d.z)));
+        } else {
+            acc[k] = a.field.add(acc[k], a.field.mul(c.x[k], (W) d.x));
+            acc[k + 1] = a.field.add(acc[k + 1], a.field.mul(c.x[k + 1], (W) d.y));
+            acc[k + 2] = a.field.add(acc[k + 2], a.field.mul(c.x[k + 2], (W) d.z));
+            acc[k + 3] = a.field.add(acc[k + 3], a.field.mul(c.x[k + 3], (W) d.w));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        d = nx;
+    }
+#else
+#pragma unroll
+    for (int e = 0; e < Cfg::E; ++e) acc[e] = a.field.add(acc[e], a.field.mul(c.x[e], (bhat + pa.origin)[(size_t) pa.lane + (size_t) e]));
+#endif
+}
+
+// d_out[r] = Fwd( N^-1 . sum_{k < terms} InvU(a[k][r]) . b^[k][r | 0] ): run_product_pass<.., PRE = true> with a loop over terms
+// between "load" and "forward".  Per resident unit: zero the accumulator; per term load the unit of a[k], run the inverse rounds,
+// acc += x . b^[k] (phase_pre_mac); then cf.x = acc * pw_scale, forward rounds, store.  The product is linear in x, so the sum is
+// scaled once: terms + 1 products per word.  Term k rebases a by k * batch * N and b^ by k * bhat_rows * N words (64-bit, wave-uniform);
+// everything else of the addressing is the prepared kernel's.  The accumulator takes the registers `keep` has in the two-operand
+// kernel, and b^ is never held across the inverse rounds: 2 x E words live, as there.  No register prefetch of a[k + 1]: it would
+// be a third E-word array beside x and acc in kernels that sit at the 128-VGPR bound already.
+// Exec: as run_product_pass; eachIF's `keep` is the accumulator, its `pre` is not used.
+template <class CI, class CF, class Exec, int M32_MODE = -1>
+NTT_HD void run_product_dot_pass(Exec &ex, const PassArgs<CI> &aa, const typename CI::W *bhat, const PassArgs<CF> &af, bool pre_bcast, int terms) {
+    using W = typename CI::W;
+    static_assert(CI::CONTIG && CF::CONTIG && CI::INV && !CF::INV, "middle of the product: inverse CONTIG then forward CONTIG");
+    static_assert(CI::LOG_M == CF::LOG_M && CI::LOG_E == CF::LOG_E && CI::LOG_NT == CF::LOG_NT && CI::R == CF::R, "same tile");
+    static_assert(CI::DIRECT_LOAD && CF::DIRECT_STORE && !CF::DMA && CI::R > 1, "register <-> HBM at both ends");
+    constexpr int R = CI::R;
+    using WL = std::integral_constant<bool, CI::WAVE_LOCAL>;
+    ex.init(aa, af);
+    static_for<0, R>([&](auto rr) {  // fill the LDS twiddle tables (once per workgroup: its hi-block is fixed)
+        constexpr int r = decltype(rr)::value;
+        if constexpr (!CI::preload(r)) ex.eachI([&](Ctx<CI> &c) { tw_table_fill<CI, r>(c, aa, ex.tabI()); });
+        if constexpr (!CF::preload(r)) ex.eachF([&](Ctx<CF> &c) { tw_table_fill<CF, r>(c, af, ex.tabF()); });
+    });
+    ex.sync(std::false_type{});
+    for (int it = 0; it < ex.ppw(); ++it) {
+        if (!(((uint64_t) ex.pg_base() + (uint64_t) it) << aa.log_up < aa.batch)) break;
+        W *const tile = ex.lds();
+        ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &cf, W *acc, W *) {
+            phase_begin_iter<CI>(ci, aa, it);
+            cf.active = ci.active;
+#pragma unroll
+            for (int e = 0; e < CI::E; ++e) acc[e] = (W) 0;  // canonical from here on (phase_pre_mac)
+        });
+        // the term strides in words: a's blocks are [batch][N], b^'s [batch][N] or -- the broadcast -- one row
+        const size_t a_stride = (size_t) aa.batch << aa.n, b_stride = pre_bcast ? (size_t) 1 << aa.n : a_stride;
+        PassArgs<CI> ak = aa;
+        const W *bk = bhat;
+        for (int k = 0; k < terms; ++k, ak.in += a_stride, bk += b_stride) {
+            ex.eachI([&](Ctx<CI> &c) { phase_load_direct_to<CI, R - 1>(c, ak, it, c.x, c.active); });
+            // A barrier per term boundary, the one the two-operand kernel has between its two inverse units: term k - 1 ended with
+            // every thread reading its round-0 words (phase_lds_read<CI, 0>), and this term begins by writing the round R - 1
+            // positions, which belong to other threads -- other waves may still be reading.  (Neither "no barrier here" argument
+            // of run_product_pass covers this edge: both rest on a thread rewriting the positions it read last itself.)
+            if (k > 0) ex.sync(WL{});
+            static_for<0, R>([&](auto kk) {
+                constexpr int r = R - 1 - decltype(kk)::value;
+                if constexpr (!CI::preload(r) && (!NTT_PRODUCT_TW_EARLY || r == R - 1))
+                    ex.eachI([&](Ctx<CI> &c) { tw_table_read<CI, r>(c, ex.tabI()); });
+                ex.eachI([&](Ctx<CI> &c) { phase_compute<CI, r, M32_MODE, true>(c, aa); });
+                if constexpr (r > 0) {
+                    ex.eachI([&](Ctx<CI> &c) { phase_lds_write<CI, r>(c, tile); });
+                    if constexpr (NTT_PRODUCT_TW_EARLY && !CI::preload(r - 1)) ex.eachI([&](Ctx<CI> &c) { tw_table_read<CI, r - 1>(c, ex.tabI()); });
+                    ex.sync(std::integral_constant<bool, CI::exchange_wave_local(r, r - 1)>{});
+                    ex.eachI([&](Ctx<CI> &c) { phase_lds_read<CI, r - 1>(c, tile); });
+                }
+            });
+            ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &, W *acc, W *) { phase_pre_mac<CI>(ci, aa, bk, it, pre_bcast, acc); });
+        }
+        // acc is canonical and so is pw_scale: one product, canonical words into the forward rounds
+        ex.eachIF([&](Ctx<CI> &, Ctx<CF> &cf, W *acc, W *) {
+#pragma unroll
+            for (int e = 0; e < CI::E; ++e) cf.x[e] = af.field.mul(acc[e], af.pw_scale);
+        });
+        // no barrier here: the forward rounds first WRITE the round-0 positions, which this thread itself read last (in the last term)
+        static_for<0, R>([&](auto kk) {
+            constexpr int r = decltype(kk)::value;
+            if constexpr (!CF::preload(r) && (!NTT_PRODUCT_TW_EARLY || r == 0))
+                ex.eachF([&](Ctx<CF> &c) { tw_table_read<CF, r>(c, ex.tabF()); });
+            ex.eachF([&](Ctx<CF> &c) { phase_compute<CF, r, M32_MODE, true>(c, af); });
+            if constexpr (r < R - 1) {
+                ex.eachF([&](Ctx<CF> &c) { phase_lds_write<CF, r>(c, tile); });
+                if constexpr (NTT_PRODUCT_TW_EARLY && !CF::preload(r + 1)) ex.eachF([&](Ctx<CF> &c) { tw_table_read<CF, r + 1>(c, ex.tabF()); });
+                ex.sync(std::integral_constant<bool, CF::exchange_wave_local(r, r + 1)>{});
+                ex.eachF([&](Ctx<CF> &c) { phase_lds_read<CF, r + 1>(c, tile); });
+            }
+        });
+        ex.eachF([&](Ctx<CF> &c) { phase_canon<CF>(c, af); });
+        ex.eachF([&](Ctx<CF> &c) { phase_store_direct<CF, R - 1>(c, af, it); });
+        // ... and none here: the next unit's first LDS write goes to the round R-1 positions this thread read last
+    }
+}
+
 // The two configurations of the product's middle pass for one unit size (Goldilocks; pass_kernel-independent so that
 // the host index model instantiates exactly what kernels_gl_product.hip launches).  Which rounds keep their twiddles in
 // registers across the batch loop (bit r): the innermost round has a different set per thread and stays resident; the

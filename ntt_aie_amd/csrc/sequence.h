@@ -328,4 +328,45 @@ int seq_polymul_pre(const PlanFacts &pf, const std::vector<host::PassDesc> &pass
     return seq_passes(pf, passes, 1, passes.size(), false, out, out, batch, LAYOUT_NATURAL, [](ErasedArgs &, size_t) {}, emit);
 }
 
+// ntt_polymul_dot_pre: out[r] = Fwd( N^-1 . sum_{k < terms} InvU(a[k][r]) . bhat[k][r | 0] ).  a is [terms][batch][N], contiguous and
+// overwritten; bhat is [terms][bhat_rows][N] canonical words in natural order (row (k, .) is what ntt_polymul_prepare writes), bhat_rows ==
+// batch or 1, never written; out is [batch][N] and may be a (term 0's block).  The decomposition is the one selected for `batch`.
+// Where polymul_dot_fused() -- polymul_fused() and a unit size whose summed middle has a kernel (launch.h: product_dot_used: all but the
+// general 64-bit modulus at 2^10 and 4-byte words at 2^13) --: the inverse column passes of a as ONE launch each over terms * batch rows (the blocks are contiguous: the
+// contiguous-operands case of seq_polymul_fused), then ONE launch that runs, per resident unit, the last inverse pass of every term
+// and sums the products with the thread's words of bhat in registers, scales by N^-1 once and runs the first forward pass (in2 = bhat,
+// in2_prepared, in2_broadcast, dot_*), then the forward column passes in place on `out`.  A single-pass size is the middle step alone.
+// Everywhere else: the unscaled inverse of all terms * batch rows in place, dot_rows(a, bhat), which leaves the scaled sum in term 0's
+// block (a launch of its own, kernels.h: launch_dot_rows), and the plain forward transform from there to `out`.
+// ONE forward transform on either path, whatever `terms`.  The caller has checked terms >= 1 and terms * batch <= 2^31 - 1.
+inline bool polymul_dot_fused(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, size_t batch) {
+    return polymul_fused(pf, passes, batch) && product_dot_used(pf.field, passes.front().log_m);
+}
+template <class Emit, class DotRows>
+int seq_polymul_dot(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, void *a, const void *bhat, size_t bhat_rows, size_t terms, void *out, size_t batch,
+                    Emit &&emit, DotRows &&dot_rows) {
+    const bool bcast = bhat_rows != batch;  // (batch == 1: the two cases are one, and the per-row addressing serves it)
+    if (!polymul_dot_fused(pf, passes, batch)) {
+        if (const int rc = seq_inverse(pf, passes, a, a, terms * batch, LAYOUT_NATURAL, 0, emit)) return rc;
+        if (const int rc = dot_rows(a, bhat)) return rc;
+        return seq_forward(pf, passes, a, out, batch, LAYOUT_NATURAL, nullptr, 1, nullptr, emit);
+    }
+    for (size_t i = passes.size(); i-- > 1;)
+        if (const int rc = emit(pass_step(pf, passes[i], (int) i, true, a, a, terms * batch, LAYOUT_NATURAL))) return rc;
+    const host::PassDesc &first = passes.front();
+    Step mid{STEP_PRODUCT, false, true, first.log_m, 0, step_args(pf, first, a, out, batch)};
+    mid.args.in2 = bhat;
+    mid.args.in2_prepared = 1;
+    mid.args.in2_broadcast = bcast ? 1 : 0;
+    mid.args.dot_terms = (int) terms;
+    mid.args.dot_in_stride = (uint64_t) batch << pf.logn;
+    mid.args.dot_in2_stride = (uint64_t) (bcast ? 1 : batch) << pf.logn;
+    mid.args.tw = pf.tw_inv;
+    mid.args.tw2 = pf.tw_fwd;
+    mid.args.layout = LAYOUT_NATURAL;
+    mid.args.pw_scale = pw_scale_form(pf, pf.ninv_plain);
+    if (const int rc = emit(mid)) return rc;
+    return seq_passes(pf, passes, 1, passes.size(), false, out, out, batch, LAYOUT_NATURAL, [](ErasedArgs &, size_t) {}, emit);
+}
+
 }  // namespace ntt

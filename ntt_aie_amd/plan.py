@@ -436,6 +436,35 @@ class NTTPlan:
                                                     self._stream(stream)), "ntt_polymul_negacyclic_pre")
         return out
 
+    def polymul_dot_pre(self, a: torch.Tensor, bhat: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """sum_k a[k]*b[k] mod (x^N + 1, p) with every b[k] given prepared (ntt_polymul_dot_pre); needs a kind-2 table.  a is
+        [K, batch, N]; bhat is [K, batch, N], one prepared operand per term and row, or [K, N] / [K, 1, N]: one per term that
+        multiplies every row (the key-switching case).  The sum runs inside the middle pass and ONE forward transform follows.
+        a is overwritten (scratch); `out`, [batch, N], defaults to a[0]; bhat is only read and must not overlap a or out."""
+        if a.dim() != 3 or a.shape[2] != self.n:
+            raise ValueError("a must be [terms, batch, N]")
+        terms, rows_a = int(a.shape[0]), int(a.shape[1])
+        if bhat.dim() == 3 and tuple(bhat.shape) == (terms, rows_a, self.n):
+            rows = rows_a
+        elif tuple(bhat.shape) in ((terms, self.n), (terms, 1, self.n)):
+            rows = 1
+        else:
+            raise ValueError("bhat must be [terms, batch, N], or [terms, N] / [terms, 1, N] (broadcast)")
+        if terms == 0:
+            raise ValueError("a has no terms")
+        out = a[0] if out is None else out
+        if out.dim() != 2 or tuple(out.shape) != (rows_a, self.n):
+            raise ValueError("out must be [batch, N]")
+        self._batch(a)
+        self._batch(out)
+        if not bhat.is_cuda or bhat.device.index != self.device:
+            raise ValueError("buffer is not on cuda:%d" % self.device)
+        if not bhat.is_contiguous() or bhat.element_size() != self.word_bytes:
+            raise ValueError("buffer must be contiguous with %d-byte words" % self.word_bytes)
+        check(_lib.lib().ntt_polymul_dot_pre(self._h, a.data_ptr(), bhat.data_ptr(), rows, terms, out.data_ptr(), rows_a,
+                                             self._stream(stream)), "ntt_polymul_dot_pre")
+        return out
+
     def count_noncanonical(self, buf: torch.Tensor) -> int:
         """How many words of `buf` are >= p (the transforms require canonical residues)."""
         b = self._batch(buf)
