@@ -130,6 +130,8 @@ int ntt_plan_get_twiddles(ntt_plan_t plan, int inverse, void *host_T);
  * 11 whether a coset-inverse shift is set (ntt_plan_set_coset_inverse), 12 whether ntt_coset_inverse on this plan scales inside
  * its last pass (1) or runs the separate row-scaling kernel after the transform (0; also 0 while nothing is set);
  * 13 number of passes of the columns decomposition (ntt_forward_columns / ntt_inverse_columns; 0 when logn < 4),
+ * 14 whether ntt_polymul_matvec_pre on this plan runs ONE middle launch per pair of outputs through the two-output kernel (1) or one
+ * summed launch per output or the unfused path (0); answered for the pinned decomposition, else for the one a batch of 1 selects,
  * 96 + i: stages in pass i of it, 128 + i: first stage of pass i of it (every pass is a column pass) */
 int64_t ntt_plan_info(ntt_plan_t plan, int what);
 
@@ -380,6 +382,32 @@ int ntt_polymul_negacyclic_pre(ntt_plan_t plan, void *d_a, const void *d_bhat, s
  * modulus where the first pass has 10 stages and of 4-byte words where it has 13: the summed middle has no kernel for those two units. */
 int ntt_polymul_dot_pre(ntt_plan_t plan, void *d_a, const void *d_bhat, size_t bhat_rows, size_t terms,
                         void *d_out, size_t batch, void *stream);
+
+/* SEVERAL negacyclic inner products of ONE operand a with prepared operands -- the two polynomials of an RLWE key switch,
+ * sum_k digit_k(a) * ksk0_k and sum_k digit_k(a) * ksk1_k, from the same digits; the rows of a module-LWE product A . s from the same s:
+ *   d_out[j][r] = Fwd( N^-1 . sum_{k < terms} InvU(d_a[k][r]) . d_bhat[j][k][bhat_rows == 1 ? 0 : r] ),  j < outs,  r < batch,  kind-2 table.
+ * d_a is [terms][batch][N] words, contiguous; it is scratch and is overwritten, as in ntt_polymul_dot_pre.  d_bhat is
+ * [outs][terms][bhat_rows][N] canonical words: block j is exactly an operand of ntt_polymul_dot_pre; it is never written.  bhat_rows is
+ * batch, or 1.  d_out is [outs][batch][N].
+ * Values: block j of d_out equals what ntt_polymul_dot_pre writes for a copy of a and block j of d_bhat, bit for bit, whatever the
+ * decomposition and on every clone.
+ * UNLIKE ntt_polymul_dot_pre, d_out may NOT overlap d_a anywhere, not even term 0's block: the middle launches of later outputs still read
+ * a.  Any overlap of d_out with the terms * batch * N words of d_a is NTT_E_ARG, as is any overlap of d_a or d_out with the
+ * outs * terms * bhat_rows * N words of d_bhat, a null or misaligned pointer, bhat_rows other than 1 or batch, terms == 0 or outs == 0 with
+ * batch > 0, and terms * batch or outs * batch > 2^31 - 1.  NTT_E_NOTABLE / NTT_E_NOTINVERTIBLE as for ntt_polymul_dot_pre; batch == 0 is
+ * NTT_OK whatever the other arguments.  The decomposition is the one ntt_plan_select(plan, batch) names, and a pinned policy is
+ * honoured.  Asynchronous on `stream`, no allocation, no host synchronisation; nothing outside the three word ranges named above is accessed.
+ * Where ntt_polymul_dot_pre runs its fused middle pass, the call is a's inverse column passes as ONE launch each over terms * batch rows --
+ * once, whatever `outs` --, then the middle launches, ONE per pair of outputs where the two-output kernel is used (4-byte words and the
+ * general 64-bit modulus, not Goldilocks: DESIGN.md section 3.2; it runs the last inverse pass of every term once and sums into two accumulators) plus one summed launch for
+ * the last output of an odd `outs`, else one summed launch per output; then the forward column passes as ONE launch each over outs * batch
+ * rows.  Derived (not measured with counters) at a two-pass size, K = terms, J = outs, paired: (2 K + ceil(J/2) K + J K + 3 J) N words of HBM
+ * traffic and K + ceil(J/2) K + 2 J half-transforms, against J (4 K + 3) N words, 2 K N more per copy of a, and J (2 K + 2) half-transforms
+ * for J calls of ntt_polymul_dot_pre.  Every other size runs the unscaled inverse over terms * batch rows, ONE small launch that writes
+ * the scaled sums of every output, and ONE plain forward transform over outs * batch rows.  No path loops over terms on the host, none
+ * transforms a more than once. */
+int ntt_polymul_matvec_pre(ntt_plan_t plan, void *d_a, const void *d_bhat, size_t bhat_rows, size_t terms, size_t outs, void *d_out,
+                           size_t batch, void *stream);
 
 /* Precondition check (blocking, diagnostic): how many of the batch*N words are >= p.  The transforms
  * assume canonical residues, as the reference's vector_modadd / vector_modsub do (src/aie_core.cc:41-62);

@@ -38,7 +38,7 @@ EXPORTS = (
     "ntt_plan_set_coset", "ntt_lde", "ntt_plan_set_coset_inverse", "ntt_coset_inverse", "ntt_forward_columns", "ntt_inverse_columns",
     "ntt_lde_columns", "ntt_coset_inverse_columns",
     "ntt_forward_profile", "ntt_inverse", "ntt_pointwise_mul", "ntt_polymul_negacyclic", "ntt_count_noncanonical", "ntt_forward_stages",
-    "ntt_polymul_prepare", "ntt_polymul_negacyclic_pre", "ntt_polymul_dot_pre",
+    "ntt_polymul_prepare", "ntt_polymul_negacyclic_pre", "ntt_polymul_dot_pre", "ntt_polymul_matvec_pre",
 )
 
 
@@ -104,6 +104,8 @@ def open_library(path: str, since_v3: bool = True) -> C.CDLL:
         L.ntt_polymul_negacyclic_pre.argtypes = [vp, vp, vp, sz, vp, sz, vp]
     if hasattr(L, "ntt_polymul_dot_pre"):
         L.ntt_polymul_dot_pre.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp]
+    if hasattr(L, "ntt_polymul_matvec_pre"):
+        L.ntt_polymul_matvec_pre.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, vp]
     L.ntt_count_noncanonical.argtypes = [vp, vp, sz, C.POINTER(C.c_uint64)]
     L.ntt_forward_stages.argtypes = [vp, vp, vp, sz, C.c_int, vp]
     return L

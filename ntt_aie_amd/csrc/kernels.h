@@ -56,7 +56,15 @@ hipError_t launch_product_dot_mid_of(int log_m, const ErasedArgs &a, hipStream_t
 extern template hipError_t launch_product_dot_mid_of<FieldGL>(int, const ErasedArgs &, hipStream_t);
 extern template hipError_t launch_product_dot_mid_of<FieldM32>(int, const ErasedArgs &, hipStream_t);
 extern template hipError_t launch_product_dot_mid_of<FieldM64>(int, const ErasedArgs &, hipStream_t);
-hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field, a.in2_prepared and a.dot_terms
+// ... for two outputs of one operand a at once (ntt_polymul_matvec_pre; a.mv_outs == 2): per unit and term ONE inverse pass of a's block,
+// two accumulators, then two forward passes -> a.out and a.out + a.mv_out_stride.  Kernels of their own under a register bound of their
+// own (run_product_mv_pass), the unit sizes of launch.h's product_mv_unit, kernels_<field>_product_mv.hip
+template <class F>
+hipError_t launch_product_mv_mid_of(int log_m, const ErasedArgs &a, hipStream_t s);
+extern template hipError_t launch_product_mv_mid_of<FieldGL>(int, const ErasedArgs &, hipStream_t);
+extern template hipError_t launch_product_mv_mid_of<FieldM32>(int, const ErasedArgs &, hipStream_t);
+extern template hipError_t launch_product_mv_mid_of<FieldM64>(int, const ErasedArgs &, hipStream_t);
+hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field, a.in2_prepared, a.dot_terms and a.mv_outs
 
 #if defined(NTT_EXPERIMENT)
 // Tools-side experiment, NOT part of libntt_hip.so (tools/fused_gl16.hip, libntt_hip_exp.so only):
@@ -78,6 +86,11 @@ hipError_t launch_pointwise_row(const FieldParams &fp, void *buf, const void *ro
 // is the scale times R^2 in table form (sequence.h: pw_scale_form); a: [terms][batch][2^n] words, bhat: [terms][bhat_rows][2^n] words, read
 // only.  The sum of ntt_polymul_dot_pre at the sizes without a fused middle
 hipError_t launch_dot_rows(const FieldParams &fp, void *a, const void *bhat, int n, size_t batch, size_t bhat_rows, size_t terms, uint64_t scale2, hipStream_t s);
+// out[j][r][i] = scale2 * sum_k a[k][r][i] * bhat[j][k][bhat_rows == 1 ? 0 : r][i] / R^2 for every j < outs, as launch_dot_rows computes it for one j;
+// a: [terms][batch][2^n] words, read only here; bhat: [outs][terms][bhat_rows][2^n] words, read only; out: [outs][batch][2^n] words, apart from
+// both.  ONE launch: the sums of ntt_polymul_matvec_pre at the sizes without a fused middle
+hipError_t launch_matvec_rows(const FieldParams &fp, const void *a, const void *bhat, void *out, int n, size_t batch, size_t bhat_rows, size_t terms, size_t outs,
+                              uint64_t scale2, hipStream_t s);
 // device-side table generation (no host upload): T[i] = base^e_kind(i), table form
 hipError_t launch_gen_table(const FieldParams &fp, void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, hipStream_t s);
 // coset vector of ntt_plan_set_coset: s[i] = shift^bitrev_logn(i mod 2^logn), table form, i < len (len = max(2^logn, 4));

@@ -83,6 +83,12 @@ struct ErasedArgs {
     int dot_terms;
     uint64_t dot_in_stride;
     uint64_t dot_in2_stride;
+    // product_mid launch of ntt_polymul_matvec_pre that sums for TWO outputs at once (run_product_mv_pass): mv_outs == 2, and a summed
+    // launch in everything else (dot_* as above, for output 0).  Output 1 reads its prepared words mv_in2_stride words after output 0's
+    // (one output's block of the operand: terms * bhat_rows * N) and stores mv_out_stride words after it (batch * N).  0: every other launch
+    int mv_outs;
+    uint64_t mv_in2_stride;
+    uint64_t mv_out_stride;
 #if defined(NTT_PHASE_STAMPS)
     void *stamps;            // diagnostic build: PassArgs::stamps / stamp_records (ntt_stamps_set)
     uint32_t stamp_records;
@@ -358,6 +364,44 @@ inline bool product_dot_used(const FieldParams &fp, int log_m) {
 inline bool product_dot_args_ok(const ErasedArgs &e) {
     const uint64_t row = (uint64_t) 1 << e.n;
     return e.dot_terms > 0 && e.in2_prepared && e.dot_in_stride == (uint64_t) e.batch * row && e.dot_in2_stride == (e.in2_broadcast ? row : (uint64_t) e.batch * row);
+}
+
+// The two-output summed middle of ntt_polymul_matvec_pre (pass.h: run_product_mv_pass): which units of product_dot_dispatch have such a
+// kernel.  It holds two E-word accumulators beside x, so it is built under a launch bound of its own (product_kernel.inc:
+// NTT_PRODUCT_MV_WPE, 3 waves per SIMD); a unit whose kernel needs scratch even there is excluded here and runs one summed launch per
+// output instead (register table and the A/B that decides per word class: DESIGN.md section 3.2).  The two units without a summed
+// kernel have none of this kind either: an odd number of outputs ends in a summed launch.
+// Goldilocks: every unit compiles without scratch, but the A/B rule -- the pair faster than two summed launches in EVERY burst at EVERY
+// shape of the class -- failed at one shape (2^12 x 4096 per row: one burst of the pair at 1.091 ms against 1.082 ms;
+// profiles/polymul_matvec_ab.txt), so the product library does not use the two-output kernel for that class.  The experiment build
+// keeps it, so that tools/bench_polymul_matvec.py can measure it again (legs Ax and C).  Those six kernels are stepped by the host model
+// compiled as the experiment build (tests/emu_product_mv_lib.py: lib(experiment=True)); on the GPU only the tool's sampled rows check them.
+template <class F>
+constexpr bool product_mv_unit(int log_m) {
+#if !defined(NTT_EXPERIMENT)
+    if (std::is_same<F, FieldGL>::value) return false;
+#endif
+    return product_dot_unit<F>(log_m);
+}
+template <class F, class Fn>
+bool product_mv_dispatch(int log_m, Fn &&fn) {
+    bool found = false;
+    product_dispatch<F>(log_m, [&](auto tag) {
+        if constexpr (product_mv_unit<F>(decltype(tag)::Cfg::CI::LOG_M)) {
+            fn(tag);
+            found = true;
+        }
+    });
+    return found;
+}
+inline bool product_mv_used(const FieldParams &fp, int log_m) {
+    return product_dot_used(fp, log_m) && with_field(fp, [&](auto f) { return product_mv_unit<decltype(f)>(log_m); });
+}
+
+// what a launch of the two-output summed middle must carry: a summed launch for output 0, and the strides to output 1
+inline bool product_mv_args_ok(const ErasedArgs &e) {
+    return product_dot_args_ok(e) && e.mv_outs == 2 && e.mv_in2_stride == (uint64_t) e.dot_terms * e.dot_in2_stride &&
+           e.mv_out_stride == (uint64_t) e.batch << e.n;
 }
 
 // one leg of the product launch: the inverse pass of an operand (in, no out) or the forward pass of the product (out, no in)

@@ -267,6 +267,44 @@ __global__ __launch_bounds__(256) void dot_rows_kernel(typename F::W *a, const t
     }
 }
 
+// The sums of ntt_polymul_matvec_pre where no fused middle pass runs: out[j][r][i] = scale2 * sum_k a[k][r][i] * bhat[j][k][r | 0][i] / R^2 for
+// every j < outs in ONE launch -- dot_rows_kernel's arithmetic, word for word, out of place: a is only read (every output needs it).
+// blockIdx.y is the output; within it one thread per 16-byte chunk of the [batch][N] block, grid-stride.  Output j's block of bhat lies
+// j * terms * b_stride words on, its block of out j * count words.  bcast: a term of bhat has EXACTLY row_mask + 1 words -- a row shorter
+// than a chunk goes word by word, so nothing past it is read.
+template <class F>
+__global__ __launch_bounds__(256) void matvec_rows_kernel(const typename F::W *a, const typename F::W *bhat, typename F::W *out, size_t count, uint32_t row_mask,
+                                                          int bcast, uint32_t terms, size_t a_stride, size_t b_stride, F f, typename F::W scale2) {
+    using W = typename F::W;
+    constexpr int V = 16 / sizeof(W);
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    bhat += (size_t) blockIdx.y * terms * b_stride;
+    out += (size_t) blockIdx.y * count;
+    const size_t chunks = row_mask + 1u >= (uint32_t) V ? count / V : 0, stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t c = (size_t) blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += stride) {
+        const size_t w = bcast ? (size_t) ((uint32_t) (c * V) & row_mask) : c * V;  // first word of the chunk inside a term of bhat
+        Vec<W, V> acc;
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc.v[k] = (W) 0;
+        for (uint32_t t = 0; t < terms; ++t) {
+            const Vec<W, V> x = *(reinterpret_cast<const Vec<W, V> *>(a + (size_t) t * a_stride) + c);  // read again by every output: cached
+            const Vec<W, V> m = *reinterpret_cast<const Vec<W, V> *>(bhat + (size_t) t * b_stride + w);
+#pragma unroll
+            for (int k = 0; k < V; ++k) acc.v[k] = f.add(acc.v[k], f.mul(x.v[k], m.v[k]));
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc.v[k] = f.mul(acc.v[k], scale2);
+        u32x4 zz;
+        __builtin_memcpy(&zz, &acc, 16);
+        __builtin_nontemporal_store(zz, reinterpret_cast<u32x4 *>(out) + c);
+    }
+    for (size_t i = chunks * V + (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        W acc = (W) 0;
+        for (uint32_t t = 0; t < terms; ++t) acc = f.add(acc, f.mul(a[(size_t) t * a_stride + i], bhat[(size_t) t * b_stride + (bcast ? (size_t) ((uint32_t) i & row_mask) : i)]));
+        out[i] = f.mul(acc, scale2);
+    }
+}
+
 // out[i] = T[i] * c, both in table (Montgomery) form: the scaled stage-0 twiddles of the inverse transform (pass.h: fold_scale)
 template <class F>
 __global__ __launch_bounds__(256) void scale_table_kernel(const typename F::W *T, typename F::W *out, size_t count,
@@ -312,6 +350,7 @@ hipError_t launch_mat_pass(bool inverse, int log_m, const ErasedArgs &a, hipStre
 
 hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s) {
     return with_field(a.field, [&](auto f) {
+        if (a.mv_outs != 0) return launch_product_mv_mid_of<decltype(f)>(log_m, a, s);
         if (a.dot_terms != 0) return launch_product_dot_mid_of<decltype(f)>(log_m, a, s);
         return a.in2_prepared ? launch_product_pre_mid_of<decltype(f)>(log_m, a, s) : launch_product_mid_of<decltype(f)>(log_m, a, s);
     });
@@ -349,6 +388,26 @@ hipError_t launch_dot_rows(const FieldParams &fp, void *a, const void *bhat, int
         hipLaunchKernelGGL(dot_rows_kernel<F>, dim3(grid_for((count + 16 / sizeof(W) - 1) / (16 / sizeof(W)))), dim3(256), 0, s, (W *) a, (const W *) bhat, count,
                            (uint32_t) (((size_t) 1 << n) - 1), bhat_rows != batch ? 1 : 0, (uint32_t) terms, count, bhat_rows << n, f, (W) scale2);
         return hipGetLastError();
+    });
+}
+
+hipError_t launch_matvec_rows(const FieldParams &fp, const void *a, const void *bhat, void *out, int n, size_t batch, size_t bhat_rows, size_t terms, size_t outs,
+                              uint64_t scale2, hipStream_t s) {
+    const size_t count = batch << n;
+    if (count == 0 || terms == 0 || outs == 0) return hipSuccess;
+    return with_field(fp, [&](auto f) {
+        using F = decltype(f);
+        using W = typename F::W;
+        // blockIdx.y is the output: one launch up to 65535 outputs, a slice per 65535 beyond
+        for (size_t j = 0; j < outs; j += 65535u) {
+            const size_t nj = outs - j < 65535u ? outs - j : 65535u;
+            hipLaunchKernelGGL(matvec_rows_kernel<F>, dim3(grid_for((count + 16 / sizeof(W) - 1) / (16 / sizeof(W))), (unsigned) nj), dim3(256), 0, s, (const W *) a,
+                               (const W *) bhat + j * terms * (bhat_rows << n), (W *) out + j * count, count, (uint32_t) (((size_t) 1 << n) - 1), bhat_rows != batch ? 1 : 0,
+                               (uint32_t) terms, count, bhat_rows << n, f, (W) scale2);
+            const hipError_t err = hipGetLastError();
+            if (err != hipSuccess) return err;
+        }
+        return hipSuccess;
     });
 }
 

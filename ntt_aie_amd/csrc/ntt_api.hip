@@ -335,6 +335,7 @@ int ntt_plan_create(ntt_plan_t *out, int logn, uint64_t p, int word_bytes, int d
     if (const char *e = getenv("NTT_FUSED")) pl->fused = atoi(e);
     if (const char *e = getenv("NTT_LDE_UNFUSED")) pl->lde_unfused = atoi(e) != 0;  // tools/bench_lde.py: leg B
     if (const char *e = getenv("NTT_COSET_INV_UNFUSED")) pl->cinv_unfused = atoi(e) != 0;  // tools/bench_coset_inverse.py: leg B
+    if (const char *e = getenv("NTT_MATVEC_SINGLE")) pl->mv_single = atoi(e) != 0;  // tools/bench_polymul_matvec.py: leg C
     if (const char *e = getenv("NTT_PLAN_SPLIT")) {  // "8,6,6" = CONTIG 8 stages + two 6-stage column passes
         std::vector<PassDesc> v;
         int s0 = 0;
@@ -496,6 +497,10 @@ int64_t ntt_plan_info(ntt_plan_t pl, int what) NTT_GUARD {
         case 11: return pl->cinv_set ? 1 : 0;
         case 12: return cinv_fused(pl) ? 1 : 0;
         case 13: return (int64_t) pl->col_passes.size();
+        case 14: {  // does ntt_polymul_matvec_pre run two-output middle launches (the pinned decomposition, or the one of a small batch)
+            const std::vector<PassDesc> &passes = passes_for(pl, 1);
+            return ntt::polymul_dot_fused(*pl, passes, 1) && ntt::polymul_matvec_paired(*pl, passes) ? 1 : 0;
+        }
         case 8: {  // capacity for ntt_forward_profile whatever the batch
             size_t k = 0;
             for (const PlanAlt &a : pl->alts) k = a.passes.size() > k ? a.passes.size() : k;
@@ -638,6 +643,7 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
         pl->lde_shift = src->lde_shift;
     }
     pl->cinv_unfused = src->cinv_unfused;
+    pl->mv_single = src->mv_single;
     if (src->cinv_set) {  // ... and the coset-interpolation setting with its vector
         const size_t bytes = cinv_u_words(src) * (size_t) src->word_bytes;
         DeviceGuard g(device);
@@ -901,6 +907,46 @@ int ntt_polymul_dot_pre(ntt_plan_t pl, void *d_a, const void *d_bhat, size_t bha
         [&](void *buf, const void *hat) {
             RoctxRange sum("product(dot): row sum");
             return (int) ntt::launch_dot_rows(pl->field, buf, hat, pl->logn, batch, bhat_rows, terms, ntt::pw_scale_form(*pl, pl->ninv_plain), s);
+        });
+} NTT_GUARD_END
+
+int ntt_polymul_matvec_pre(ntt_plan_t pl, void *d_a, const void *d_bhat, size_t bhat_rows, size_t terms, size_t outs, void *d_out, size_t batch,
+                           void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_a, d_bhat, batch);
+    if (rc) return rc;
+    if (batch && (!d_out || ((uintptr_t) d_out & 15u))) return NTT_E_ARG;
+    if (batch && bhat_rows != 1 && bhat_rows != batch) return NTT_E_ARG;
+    if (batch && (terms == 0 || terms > 0x7FFFFFFFull / batch)) return NTT_E_ARG;  // the inverse passes run over terms * batch rows
+    if (batch && (outs == 0 || outs > 0x7FFFFFFFull / batch)) return NTT_E_ARG;    // the forward passes over outs * batch rows
+    if (!pl->has_table) return NTT_E_NOTABLE;
+    if (!pl->has_inv) return NTT_E_NOTINVERTIBLE;
+    if (batch == 0) return NTT_OK;
+    {
+        using u128 = unsigned __int128;
+        const u128 row = table_bytes(pl), top = (u128) 1 << 63;  // no buffer ends beyond that: three ranges that cannot wrap
+        const u128 a0 = (uintptr_t) d_a, a1 = a0 + (u128) terms * batch * row, o0 = (uintptr_t) d_out, o1 = o0 + (u128) outs * batch * row;
+        const u128 h0 = (uintptr_t) d_bhat, h1 = h0 + (u128) outs * terms * bhat_rows * row;
+        if (a1 > top || o1 > top || h1 > top) return NTT_E_ARG;
+        // out lies apart from all of a -- the middle launches of later outputs still read a -- and bhat, which is read while a and out
+        // are written, apart from both
+        if ((o0 < a1 && a0 < o1) || (a0 < h1 && h0 < a1) || (o0 < h1 && h0 < o1)) return NTT_E_ARG;
+    }
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    hipStream_t s = (hipStream_t) stream;
+    RoctxRange whole("ntt_polymul_matvec_pre");
+    const std::vector<PassDesc> &passes = passes_for(pl, batch);  // by batch, as ntt_polymul_dot_pre selects it
+    return ntt::seq_polymul_matvec(
+        *pl, passes, d_a, d_bhat, bhat_rows, terms, outs, d_out, batch,
+        [&](const ntt::Step &st) {
+            return launch_step(st.family == ntt::STEP_PRODUCT ? (st.args.mv_outs ? "product(matvec): fused middle, two outputs" : "product(matvec): fused middle")
+                               : st.inverse                   ? "product(matvec): inv pass"
+                                                              : "product(matvec): fwd pass",
+                               st, s);
+        },
+        [&](void *buf, const void *hat, void *out) {
+            RoctxRange sum("product(matvec): row sums");
+            return (int) ntt::launch_matvec_rows(pl->field, buf, hat, out, pl->logn, batch, bhat_rows, terms, outs, ntt::pw_scale_form(*pl, pl->ninv_plain), s);
         });
 } NTT_GUARD_END
 

@@ -2010,6 +2010,98 @@ NTT_HD void run_product_dot_pass(Exec &ex, const PassArgs<CI> &aa, const typenam
     }
 }
 
+// ---- two inner products of ONE operand a (ntt_polymul_matvec_pre): the summed middle with two accumulators ---------------------
+// out[j][r] = Fwd( N^-1 . sum_{k < terms} InvU(a[k][r]) . b^[j][k][r | 0] ), j = 0, 1: run_product_dot_pass with the inverse rounds of
+// a[k] shared between two outputs.  Per resident unit: zero both accumulators; per term load the unit of a[k], run the inverse rounds,
+// acc0 += x . b^[0][k] and acc1 += x . b^[1][k] (phase_pre_mac twice: the same address rule, output 1's block of b^ lies b_out_stride
+// words on); then per output cf.x = acc_j * pw_scale, forward rounds, canonical words to that output's block (output 1's lies
+// o_out_stride words on).  Every word of an output goes through exactly the operations run_product_dot_pass applies to it, in the
+// same order: the words are that kernel's, bit for bit.  K inverse units and 2 forward units instead of 2 K + 2.
+// Three E-word arrays are live in the term loop (x and both accumulators): the kernel is built under a register bound of its own
+// (product_kernel.inc: NTT_PRODUCT_MV_WPE).
+// Exec: as run_product_pass; eachIF's `keep` and `pre` are the two accumulators.
+template <class CI, class CF, class Exec, int M32_MODE = -1>
+NTT_HD void run_product_mv_pass(Exec &ex, const PassArgs<CI> &aa, const typename CI::W *bhat, const PassArgs<CF> &af, bool pre_bcast, int terms, size_t b_out_stride,
+                                size_t o_out_stride) {
+    using W = typename CI::W;
+    static_assert(CI::CONTIG && CF::CONTIG && CI::INV && !CF::INV, "middle of the product: inverse CONTIG then forward CONTIG");
+    static_assert(CI::LOG_M == CF::LOG_M && CI::LOG_E == CF::LOG_E && CI::LOG_NT == CF::LOG_NT && CI::R == CF::R, "same tile");
+    static_assert(CI::DIRECT_LOAD && CF::DIRECT_STORE && !CF::DMA && CI::R > 1, "register <-> HBM at both ends");
+    constexpr int R = CI::R;
+    using WL = std::integral_constant<bool, CI::WAVE_LOCAL>;
+    ex.init(aa, af);
+    static_for<0, R>([&](auto rr) {  // fill the LDS twiddle tables (once per workgroup: its hi-block is fixed)
+        constexpr int r = decltype(rr)::value;
+        if constexpr (!CI::preload(r)) ex.eachI([&](Ctx<CI> &c) { tw_table_fill<CI, r>(c, aa, ex.tabI()); });
+        if constexpr (!CF::preload(r)) ex.eachF([&](Ctx<CF> &c) { tw_table_fill<CF, r>(c, af, ex.tabF()); });
+    });
+    ex.sync(std::false_type{});
+    PassArgs<CF> af1 = af;  // the forward leg of output 1: the same launch, its block of out
+    af1.out = af.out + o_out_stride;
+    for (int it = 0; it < ex.ppw(); ++it) {
+        if (!(((uint64_t) ex.pg_base() + (uint64_t) it) << aa.log_up < aa.batch)) break;
+        W *const tile = ex.lds();
+        ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &cf, W *acc0, W *acc1) {
+            phase_begin_iter<CI>(ci, aa, it);
+            cf.active = ci.active;
+#pragma unroll
+            for (int e = 0; e < CI::E; ++e) acc0[e] = acc1[e] = (W) 0;  // canonical from here on (phase_pre_mac)
+        });
+        const size_t a_stride = (size_t) aa.batch << aa.n, b_stride = pre_bcast ? (size_t) 1 << aa.n : a_stride;
+        PassArgs<CI> ak = aa;
+        const W *bk = bhat;
+        for (int k = 0; k < terms; ++k, ak.in += a_stride, bk += b_stride) {
+            ex.eachI([&](Ctx<CI> &c) { phase_load_direct_to<CI, R - 1>(c, ak, it, c.x, c.active); });
+            // the barrier per term boundary of run_product_dot_pass; for k == 0 the edge is the one from the previous unit (below)
+            if (k > 0) ex.sync(WL{});
+            static_for<0, R>([&](auto kk) {
+                constexpr int r = R - 1 - decltype(kk)::value;
+                if constexpr (!CI::preload(r) && (!NTT_PRODUCT_TW_EARLY || r == R - 1))
+                    ex.eachI([&](Ctx<CI> &c) { tw_table_read<CI, r>(c, ex.tabI()); });
+                ex.eachI([&](Ctx<CI> &c) { phase_compute<CI, r, M32_MODE, true>(c, aa); });
+                if constexpr (r > 0) {
+                    ex.eachI([&](Ctx<CI> &c) { phase_lds_write<CI, r>(c, tile); });
+                    if constexpr (NTT_PRODUCT_TW_EARLY && !CI::preload(r - 1)) ex.eachI([&](Ctx<CI> &c) { tw_table_read<CI, r - 1>(c, ex.tabI()); });
+                    ex.sync(std::integral_constant<bool, CI::exchange_wave_local(r, r - 1)>{});
+                    ex.eachI([&](Ctx<CI> &c) { phase_lds_read<CI, r - 1>(c, tile); });
+                }
+            });
+            // one output after the other, each with the two-loads-in-flight fence of phase_pre_mac: x stays, b^ is never held
+            ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &, W *acc0, W *) { phase_pre_mac<CI>(ci, aa, bk, it, pre_bcast, acc0); });
+            ex.eachIF([&](Ctx<CI> &ci, Ctx<CF> &, W *, W *acc1) { phase_pre_mac<CI>(ci, aa, bk + b_out_stride, it, pre_bcast, acc1); });
+        }
+        static_for<0, 2>([&](auto jj) {
+            constexpr int j = decltype(jj)::value;
+            const PassArgs<CF> &afj = j == 0 ? af : af1;
+            ex.eachIF([&](Ctx<CI> &, Ctx<CF> &cf, W *acc0, W *acc1) {
+                const W *acc = j == 0 ? acc0 : acc1;
+#pragma unroll
+                for (int e = 0; e < CI::E; ++e) cf.x[e] = af.field.mul(acc[e], af.pw_scale);
+            });
+            // Output 0: no barrier, as in run_product_dot_pass -- the forward rounds first WRITE the round-0 positions, which this
+            // thread itself read last (in the last term).  Output 1: a barrier.  Output 0 ended with every thread reading its round
+            // R - 1 positions (phase_lds_read<CF, R - 1>), and output 1 begins by writing the round-0 positions, which belong to
+            // other threads -- other waves may still be reading.
+            if constexpr (j > 0) ex.sync(WL{});
+            static_for<0, R>([&](auto kk) {
+                constexpr int r = decltype(kk)::value;
+                if constexpr (!CF::preload(r) && (!NTT_PRODUCT_TW_EARLY || r == 0))
+                    ex.eachF([&](Ctx<CF> &c) { tw_table_read<CF, r>(c, ex.tabF()); });
+                ex.eachF([&](Ctx<CF> &c) { phase_compute<CF, r, M32_MODE, true>(c, af); });
+                if constexpr (r < R - 1) {
+                    ex.eachF([&](Ctx<CF> &c) { phase_lds_write<CF, r>(c, tile); });
+                    if constexpr (NTT_PRODUCT_TW_EARLY && !CF::preload(r + 1)) ex.eachF([&](Ctx<CF> &c) { tw_table_read<CF, r + 1>(c, ex.tabF()); });
+                    ex.sync(std::integral_constant<bool, CF::exchange_wave_local(r, r + 1)>{});
+                    ex.eachF([&](Ctx<CF> &c) { phase_lds_read<CF, r + 1>(c, tile); });
+                }
+            });
+            ex.eachF([&](Ctx<CF> &c) { phase_canon<CF>(c, af); });
+            ex.eachF([&](Ctx<CF> &c) { phase_store_direct<CF, R - 1>(c, afj, it); });
+        });
+        // ... and none here: the next unit's first LDS write goes to the round R-1 positions this thread read last (in output 1)
+    }
+}
+
 // The two configurations of the product's middle pass for one unit size (Goldilocks; pass_kernel-independent so that
 // the host index model instantiates exactly what kernels_gl_product.hip launches).  Which rounds keep their twiddles in
 // registers across the batch loop (bit r): the innermost round has a different set per thread and stays resident; the

@@ -2,7 +2,9 @@
 // run_product_pass).  Included by the three kernels_<field>_product.hip translation units, which define NTT_FIELD, and by the three
 // kernels_<field>_product_pre.hip ones, which define NTT_PRODUCT_PRE as well: the same middle with operand b prepared
 // (run_product_pass<.., PRE = true>, ntt_polymul_negacyclic_pre), and by the three kernels_<field>_product_dot.hip ones, which define
-// NTT_PRODUCT_DOT: that middle summed over the terms of an inner product (run_product_dot_pass, ntt_polymul_dot_pre).
+// NTT_PRODUCT_DOT: that middle summed over the terms of an inner product (run_product_dot_pass, ntt_polymul_dot_pre), and by the three
+// kernels_<field>_product_mv.hip ones, which define NTT_PRODUCT_MV: the summed middle for two outputs at once (run_product_mv_pass,
+// ntt_polymul_matvec_pre).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -18,7 +20,8 @@ struct GpuProductExec {
     Ctx<CF> cf;
     W keep[CI::E];  // the transformed words of operand a while operand b is transformed (unused, and gone, when b is prepared);
                     // the accumulator of an inner product
-    W pre[CI::E];   // register prefetch: operand b of this unit -- its round R-1 words, or its prepared round-0 words
+    W pre[CI::E];   // register prefetch: operand b of this unit -- its round R-1 words, or its prepared round-0 words;
+                    // the second accumulator of the two-output inner product
     W *tile, *tab_i, *tab_f;
     __device__ __forceinline__ void init(const PassArgs<CI> &aa, const PassArgs<CF> &af) {
         phase_init<CI>(ci, aa, threadIdx.x, blockIdx.x, blockIdx.y);
@@ -110,6 +113,30 @@ void product_dot_kernel(PassArgs<CI> aa, const typename CI::W *bhat, int bcast, 
     }
 }
 
+// ... for TWO outputs of one operand a: output 1 reads its prepared words b_out_stride words after output 0's and stores o_out_stride
+// words after it.  x and two accumulators are live in the term loop, which does not fit 128 VGPRs: a register bound of its own
+#ifndef NTT_PRODUCT_MV_WPE
+#define NTT_PRODUCT_MV_WPE 3  // waves per SIMD (168 VGPRs): DESIGN.md section 3.2 has the table
+#endif
+template <class CI, class CF>
+__global__ __launch_bounds__(CI::NT, NTT_PRODUCT_MV_WPE)
+void product_mv_kernel(PassArgs<CI> aa, const typename CI::W *bhat, int bcast, int terms, size_t b_out_stride, size_t o_out_stride, PassArgs<CF> af) {
+    __shared__ __attribute__((aligned(16))) typename CI::W tile[CI::LDS_WORDS];
+    __shared__ __attribute__((aligned(16))) typename CI::W tab_i[tw_table_words<CI>()];
+    __shared__ __attribute__((aligned(16))) typename CI::W tab_f[tw_table_words<CF>()];
+    GpuProductExec<CI, CF> ex;
+    ex.tile = tile;
+    ex.tab_i = tab_i;
+    ex.tab_f = tab_f;
+    if constexpr (std::is_same<typename CI::F, FieldM32>::value) {
+        if (aa.field.p < 0x40000000u) run_product_mv_pass<CI, CF, GpuProductExec<CI, CF>, 0>(ex, aa, bhat, af, bcast != 0, terms, b_out_stride, o_out_stride);
+        else if (aa.field.p < 0x80000000u) run_product_mv_pass<CI, CF, GpuProductExec<CI, CF>, 1>(ex, aa, bhat, af, bcast != 0, terms, b_out_stride, o_out_stride);
+        else run_product_mv_pass<CI, CF, GpuProductExec<CI, CF>, 2>(ex, aa, bhat, af, bcast != 0, terms, b_out_stride, o_out_stride);
+    } else {
+        run_product_mv_pass<CI, CF>(ex, aa, bhat, af, bcast != 0, terms, b_out_stride, o_out_stride);
+    }
+}
+
 template <class PC, bool PRE>
 hipError_t launch_product(const ErasedArgs &e, hipStream_t s) {
     using CI = typename PC::CI;
@@ -144,10 +171,34 @@ hipError_t launch_product_dot(const ErasedArgs &e, hipStream_t s) {
     return hipGetLastError();
 }
 
+template <class PC>
+hipError_t launch_product_mv(const ErasedArgs &e, hipStream_t s) {
+    using CI = typename PC::CI;
+    using CF = typename PC::CF;
+    if (!product_mv_args_ok(e)) return hipErrorInvalidValue;
+    const PassGeom g = product_geometry<PC>(e.n, e.batch, e.target_wgs);
+    if (g.grid_y == 0) return hipSuccess;
+    if (g.grid_y > 65535u) return hipErrorInvalidValue;  // callers fall back to the separate passes (launch.h: product_mid_fits)
+    PassArgs<CI> aa;
+    PassArgs<CF> af;
+    fill_product_args<PC>(e, g, aa, af);
+    hipLaunchKernelGGL((product_mv_kernel<CI, CF>), dim3(g.grid_x, g.grid_y, 1), dim3(CI::NT, 1, 1), 0, s, aa, (const typename CI::W *) e.in2, e.in2_broadcast,
+                       e.dot_terms, (size_t) e.mv_in2_stride, (size_t) e.mv_out_stride, af);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 // every unit size with a kernel (launch.h: product_dispatch); instantiated for this unit's field only, as launch_pass_of is (kernels.h)
-#if defined(NTT_PRODUCT_DOT)
+#if defined(NTT_PRODUCT_MV)
+template <class F>
+hipError_t launch_product_mv_mid_of(int log_m, const ErasedArgs &a, hipStream_t s) {
+    hipError_t err = hipErrorInvalidValue;
+    product_mv_dispatch<F>(log_m, [&](auto tag) { err = launch_product_mv<typename decltype(tag)::Cfg>(a, s); });
+    return err;
+}
+template hipError_t launch_product_mv_mid_of<NTT_FIELD>(int, const ErasedArgs &, hipStream_t);
+#elif defined(NTT_PRODUCT_DOT)
 template <class F>
 hipError_t launch_product_dot_mid_of(int log_m, const ErasedArgs &a, hipStream_t s) {
     hipError_t err = hipErrorInvalidValue;

@@ -44,6 +44,7 @@ struct PlanFacts {
     int only_pass = -1;      // NTT_ONLY_PASS=k: a forward run of passes launches pass k alone (power / clock of one kernel)
     int lde_unfused = 0;     // NTT_LDE_UNFUSED=1: ntt_lde takes the separate expansion kernel at every size
     int cinv_unfused = 0;    // NTT_COSET_INV_UNFUSED=1: ntt_coset_inverse takes the separate row-scaling kernel at every size
+    int mv_single = 0;       // NTT_MATVEC_SINGLE=1: ntt_polymul_matvec_pre runs one summed middle launch per output, no two-output kernel
 };
 
 #if defined(NTT_PHASE_STAMPS)
@@ -367,6 +368,60 @@ int seq_polymul_dot(const PlanFacts &pf, const std::vector<host::PassDesc> &pass
     mid.args.pw_scale = pw_scale_form(pf, pf.ninv_plain);
     if (const int rc = emit(mid)) return rc;
     return seq_passes(pf, passes, 1, passes.size(), false, out, out, batch, LAYOUT_NATURAL, [](ErasedArgs &, size_t) {}, emit);
+}
+
+// ntt_polymul_matvec_pre: out[j][r] = Fwd( N^-1 . sum_{k < terms} InvU(a[k][r]) . bhat[j][k][r | 0] ), j < outs: `outs` inner products of
+// ONE operand a.  a is [terms][batch][N], contiguous and overwritten; bhat is [outs][terms][bhat_rows][N], block j an operand of
+// seq_polymul_dot, never written; out is [outs][batch][N] and lies apart from a (the middle launches of later outputs still read a).
+// Where polymul_dot_fused(): a's inverse column passes as ONE launch each over terms * batch rows -- once, whatever `outs` --, then the
+// middle launches: ONE per pair of outputs (2g, 2g + 1) through the two-output kernel (mv_*; launch.h: product_mv_used) and, for an odd
+// `outs`, the summed launch of seq_polymul_dot for the last output with in2 and out rebased; a unit without a two-output kernel runs
+// that summed launch once per output.  Then the forward column passes, ONE launch each over outs * batch rows in place on `out` (the
+// blocks are contiguous).  A single-pass size is the middle launches alone.
+// Everywhere else: the unscaled inverse of all terms * batch rows in place, mv_rows(a, bhat, out), ONE launch that writes the scaled sums
+// of every output (kernels.h: launch_matvec_rows), and ONE plain forward transform over outs * batch rows in place on `out`.
+// No path has a loop of `terms` launches and none transforms a more than once.  The caller has checked terms, outs >= 1 and
+// terms * batch, outs * batch <= 2^31 - 1.
+inline bool polymul_matvec_paired(const PlanFacts &pf, const std::vector<host::PassDesc> &passes) {
+    return product_mv_used(pf.field, passes.front().log_m) && !pf.mv_single;
+}
+template <class Emit, class MvRows>
+int seq_polymul_matvec(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, void *a, const void *bhat, size_t bhat_rows, size_t terms, size_t outs, void *out,
+                       size_t batch, Emit &&emit, MvRows &&mv_rows) {
+    const bool bcast = bhat_rows != batch;  // (batch == 1: the two cases are one, and the per-row addressing serves it)
+    if (!polymul_dot_fused(pf, passes, batch)) {
+        if (const int rc = seq_inverse(pf, passes, a, a, terms * batch, LAYOUT_NATURAL, 0, emit)) return rc;
+        if (const int rc = mv_rows(a, bhat, out)) return rc;
+        return seq_forward(pf, passes, out, out, outs * batch, LAYOUT_NATURAL, nullptr, 1, nullptr, emit);
+    }
+    for (size_t i = passes.size(); i-- > 1;)
+        if (const int rc = emit(pass_step(pf, passes[i], (int) i, true, a, a, terms * batch, LAYOUT_NATURAL))) return rc;
+    const host::PassDesc &first = passes.front();
+    const bool paired = polymul_matvec_paired(pf, passes);
+    const uint64_t row = (uint64_t) 1 << pf.logn, in2_stride = (bcast ? 1 : (uint64_t) batch) * row;
+    const size_t out_bytes = (size_t) (batch * row) * (size_t) pf.word_bytes, bhat_bytes = (size_t) (terms * in2_stride) * (size_t) pf.word_bytes;  // of ONE output
+    for (size_t j = 0; j < outs;) {
+        const bool two = paired && j + 1 < outs;
+        Step mid{STEP_PRODUCT, false, true, first.log_m, 0, step_args(pf, first, a, (char *) out + j * out_bytes, batch)};
+        mid.args.in2 = (const char *) bhat + j * bhat_bytes;
+        mid.args.in2_prepared = 1;
+        mid.args.in2_broadcast = bcast ? 1 : 0;
+        mid.args.dot_terms = (int) terms;
+        mid.args.dot_in_stride = batch * row;
+        mid.args.dot_in2_stride = in2_stride;
+        if (two) {
+            mid.args.mv_outs = 2;
+            mid.args.mv_in2_stride = terms * in2_stride;
+            mid.args.mv_out_stride = batch * row;
+        }
+        mid.args.tw = pf.tw_inv;
+        mid.args.tw2 = pf.tw_fwd;
+        mid.args.layout = LAYOUT_NATURAL;
+        mid.args.pw_scale = pw_scale_form(pf, pf.ninv_plain);
+        if (const int rc = emit(mid)) return rc;
+        j += two ? 2 : 1;
+    }
+    return seq_passes(pf, passes, 1, passes.size(), false, out, out, outs * batch, LAYOUT_NATURAL, [](ErasedArgs &, size_t) {}, emit);
 }
 
 }  // namespace ntt

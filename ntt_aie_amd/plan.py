@@ -465,6 +465,38 @@ class NTTPlan:
                                              self._stream(stream)), "ntt_polymul_dot_pre")
         return out
 
+    def polymul_matvec_pre(self, a: torch.Tensor, bhat: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """out[j] = sum_k a[k]*b[j][k] mod (x^N + 1, p) for every j, all b[j][k] given prepared (ntt_polymul_matvec_pre); needs a kind-2
+        table.  a is [K, batch, N]; bhat is [J, K, batch, N], one prepared operand per output, term and row, or [J, K, N] / [J, K, 1, N]:
+        one per output and term that multiplies every row (the key-switching case).  a is transformed once for all J outputs.  a is
+        overwritten (scratch); `out`, [J, batch, N], is allocated when not given and must not overlap a (unlike polymul_dot_pre's);
+        bhat is only read and must not overlap a or out."""
+        if a.dim() != 3 or a.shape[2] != self.n:
+            raise ValueError("a must be [terms, batch, N]")
+        terms, rows_a = int(a.shape[0]), int(a.shape[1])
+        if bhat.dim() == 4 and tuple(bhat.shape[1:]) == (terms, rows_a, self.n):
+            rows = rows_a
+        elif (bhat.dim() == 3 and tuple(bhat.shape[1:]) == (terms, self.n)) or (bhat.dim() == 4 and tuple(bhat.shape[1:]) == (terms, 1, self.n)):
+            rows = 1
+        else:
+            raise ValueError("bhat must be [outs, terms, batch, N], or [outs, terms, N] / [outs, terms, 1, N] (broadcast)")
+        outs = int(bhat.shape[0])
+        if terms == 0 or outs == 0:
+            raise ValueError("a has no terms" if terms == 0 else "bhat has no outputs")
+        if out is None:
+            out = torch.empty((outs, rows_a, self.n), dtype=a.dtype, device=a.device)
+        if out.dim() != 3 or tuple(out.shape) != (outs, rows_a, self.n):
+            raise ValueError("out must be [outs, batch, N]")
+        self._batch(a)
+        self._batch(out)
+        if not bhat.is_cuda or bhat.device.index != self.device:
+            raise ValueError("buffer is not on cuda:%d" % self.device)
+        if not bhat.is_contiguous() or bhat.element_size() != self.word_bytes:
+            raise ValueError("buffer must be contiguous with %d-byte words" % self.word_bytes)
+        check(_lib.lib().ntt_polymul_matvec_pre(self._h, a.data_ptr(), bhat.data_ptr(), rows, terms, outs, out.data_ptr(), rows_a,
+                                                self._stream(stream)), "ntt_polymul_matvec_pre")
+        return out
+
     def count_noncanonical(self, buf: torch.Tensor) -> int:
         """How many words of `buf` are >= p (the transforms require canonical residues)."""
         b = self._batch(buf)
