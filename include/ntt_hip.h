@@ -132,6 +132,8 @@ int ntt_plan_get_twiddles(ntt_plan_t plan, int inverse, void *host_T);
  * 13 number of passes of the columns decomposition (ntt_forward_columns / ntt_inverse_columns; 0 when logn < 4),
  * 14 whether ntt_polymul_matvec_pre on this plan runs ONE middle launch per pair of outputs through the two-output kernel (1) or one
  * summed launch per output or the unfused path (0); answered for the pinned decomposition, else for the one a batch of 1 selects,
+ * 15 whether ntt_polymul_gadget_pre on this plan decomposes inside the middle launch (1) or runs the decomposition kernel first (0);
+ * answered by the rule of item 14: for the pinned decomposition, else for the one a batch of 1 selects,
  * 96 + i: stages in pass i of it, 128 + i: first stage of pass i of it (every pass is a column pass) */
 int64_t ntt_plan_info(ntt_plan_t plan, int what);
 
@@ -408,6 +410,48 @@ int ntt_polymul_dot_pre(ntt_plan_t plan, void *d_a, const void *d_bhat, size_t b
  * transforms a more than once. */
 int ntt_polymul_matvec_pre(ntt_plan_t plan, void *d_a, const void *d_bhat, size_t bhat_rows, size_t terms, size_t outs, void *d_out,
                            size_t batch, void *stream);
+
+/* BALANCED GADGET DECOMPOSITION -- the digit_k(a) of the examples above, for all three word classes.  Parameters log_base = w (B = 2^w),
+ * levels = K, low_bits = l; p is the plan's modulus.  For a canonical word a, in integers (not residues):
+ *   s = +1, m = a          if a <= (p - 1) / 2,  else  s = -1, m = p - a                (centred magnitude, m <= (p - 1) / 2 < 2^63)
+ *   u = (m + h) >> l,      h = 2^(l - 1) for l > 0, else 0                              (rounds half away from zero)
+ *   v = u + C,             C = sum_{k < K - 1} 2^(k w + w - 1)                          (only the lower K - 1 digits are biased)
+ *   e_k = ((v >> k w) & (B - 1)) - B / 2  for k < K - 1, in [-B/2, B/2);   e_{K-1} = v >> (K - 1) w, unmasked, non-negative
+ *   digit_k(a) = s . e_k mod p, a canonical word.
+ * Then sum_k e_k B^k = u exactly, |s m - s u 2^l| <= 2^(l - 1), and digit_k(p - a) = -digit_k(a) mod p.
+ * Argument rule (anything else is NTT_E_ARG): 1 <= w <= 31, K >= 1, 0 <= l, l + (K - 1) w <= 63 (v then fits 64 unsigned bits for every
+ * p < 2^64), 2^(w - 1) < p, and (u_max >> (K - 1) w) + 1 < p with u_max = ((p - 1) / 2 + h) >> l (every digit then has a magnitude below p).
+ * Goldilocks with (w, K, l) = (16, 4, 0) is legal and exact; (8, 3, 40) is the usual approximate TFHE setting.
+ *
+ * ntt_gadget_decompose: d_a is [polys][batch][N] canonical words, never written; d_digits is [polys][levels][batch][N], word
+ * (q, k, r, i) = digit_k(d_a[q][r][i]) -- with t = q * levels + k exactly an operand `a` of ntt_polymul_dot_pre / ntt_polymul_matvec_pre with
+ * terms = polys * levels.  The two byte ranges must lie apart; null or misaligned pointers, polys == 0 and polys * levels * batch >
+ * 2^31 - 1 are NTT_E_ARG; batch == 0 is NTT_OK.  ONE small launch; needs only p, so it works before twiddles are set. */
+int ntt_gadget_decompose(ntt_plan_t plan, const void *d_a, size_t polys, size_t batch, int log_base, int levels, int low_bits, void *d_digits,
+                         void *stream);
+
+/* TFHE external product / key switch FROM COEFFICIENTS: ntt_polymul_matvec_pre of the gadget digits of a, decomposed on the way:
+ *   d_out[j][r] = Fwd( N^-1 . sum_t InvU(digit_{t mod K}(d_a[t div K][r])) . d_bhat[j][t][bhat_rows == 1 ? 0 : r] ),  t < polys * levels, j < outs.
+ * d_a is [polys][batch][N] canonical words; it is CONST and left intact on every path -- the one behavioural difference from the other
+ * products.  d_bhat is [outs][polys * levels][bhat_rows][N], as for ntt_polymul_matvec_pre; d_out is [outs][batch][N].  d_work is caller
+ * scratch of polys * levels * batch * N words, required non-null; its contents afterwards are unspecified and the fused path may leave it
+ * untouched (no hidden allocation, as everywhere in this library).
+ * Values: block j of d_out equals, bit for bit, what ntt_polymul_matvec_pre writes when it is given ntt_gadget_decompose's output as a,
+ * for every decomposition alternative and on every clone.
+ * All four ranges (d_a, d_work, d_bhat, d_out) are pairwise disjoint, else NTT_E_ARG.  The other rules are those of
+ * ntt_polymul_matvec_pre with terms = polys * levels (null or misaligned pointer, bhat_rows not 1 or batch, polys == 0 or outs == 0 with
+ * batch > 0, the 2^31 - 1 row limits, NTT_E_NOTABLE / NTT_E_NOTINVERTIBLE, batch == 0 is NTT_OK whatever the other arguments), plus the
+ * argument rule of the decomposition.  Asynchronous on `stream`, no allocation, no host synchronisation; the decomposition is
+ * selected by `batch`, and a pinned policy is honoured.
+ * Where the plan runs ONE pass for this batch, ntt_polymul_dot_pre runs its fused middle and the unit has digit kernels
+ * (ntt_plan_info 15), the call is the middle launches alone -- one per pair of outputs where the two-output kernel
+ * is used plus one for an odd last output, else one per output -- which read d_a directly and decompose in registers.  Derived (not
+ * measured with counters), P = polys, K = levels, J = outs, broadcast b^: (P + J) N words of HBM traffic per row (the K - 1 re-reads of a
+ * unit are expected to come from cache) against (P + 2 P K + J) N and one more launch.  Everywhere else -- a multi-pass size, a size
+ * without a fused middle, a unit without a digit kernel, a pinned alternative without a middle -- ONE launch of the decomposition
+ * kernel d_a -> d_work, then exactly ntt_polymul_matvec_pre on d_work. */
+int ntt_polymul_gadget_pre(ntt_plan_t plan, const void *d_a, size_t polys, int log_base, int levels, int low_bits, void *d_work,
+                           const void *d_bhat, size_t bhat_rows, size_t outs, void *d_out, size_t batch, void *stream);
 
 /* Precondition check (blocking, diagnostic): how many of the batch*N words are >= p.  The transforms
  * assume canonical residues, as the reference's vector_modadd / vector_modsub do (src/aie_core.cc:41-62);

@@ -39,6 +39,7 @@ EXPORTS = (
     "ntt_lde_columns", "ntt_coset_inverse_columns",
     "ntt_forward_profile", "ntt_inverse", "ntt_pointwise_mul", "ntt_polymul_negacyclic", "ntt_count_noncanonical", "ntt_forward_stages",
     "ntt_polymul_prepare", "ntt_polymul_negacyclic_pre", "ntt_polymul_dot_pre", "ntt_polymul_matvec_pre",
+    "ntt_gadget_decompose", "ntt_polymul_gadget_pre",
 )
 
 
@@ -106,6 +107,10 @@ def open_library(path: str, since_v3: bool = True) -> C.CDLL:
         L.ntt_polymul_dot_pre.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp]
     if hasattr(L, "ntt_polymul_matvec_pre"):
         L.ntt_polymul_matvec_pre.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, vp]
+    if hasattr(L, "ntt_gadget_decompose"):
+        L.ntt_gadget_decompose.argtypes = [vp, vp, sz, sz, C.c_int, C.c_int, C.c_int, vp, vp]
+    if hasattr(L, "ntt_polymul_gadget_pre"):
+        L.ntt_polymul_gadget_pre.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, vp, vp, sz, sz, vp, sz, vp]
     L.ntt_count_noncanonical.argtypes = [vp, vp, sz, C.POINTER(C.c_uint64)]
     L.ntt_forward_stages.argtypes = [vp, vp, vp, sz, C.c_int, vp]
     return L

@@ -64,7 +64,16 @@ hipError_t launch_product_mv_mid_of(int log_m, const ErasedArgs &a, hipStream_t 
 extern template hipError_t launch_product_mv_mid_of<FieldGL>(int, const ErasedArgs &, hipStream_t);
 extern template hipError_t launch_product_mv_mid_of<FieldM32>(int, const ErasedArgs &, hipStream_t);
 extern template hipError_t launch_product_mv_mid_of<FieldM64>(int, const ErasedArgs &, hipStream_t);
-hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field, a.in2_prepared, a.dot_terms and a.mv_outs
+// ... the digit variants of the last two (ntt_polymul_gadget_pre; a.gad_levels > 0): a.in is [a.dot_terms / a.gad_levels][batch][N]
+// canonical words, decomposed in registers between the load and the first inverse round (pass.h: gadget_digit); a summed launch, or a
+// two-output one (a.mv_outs == 2) where the unit has that kernel.  The unit sizes of launch.h's product_gadget_unit,
+// kernels_<field>_product_gad.hip
+template <class F>
+hipError_t launch_product_gad_mid_of(int log_m, const ErasedArgs &a, hipStream_t s);
+extern template hipError_t launch_product_gad_mid_of<FieldGL>(int, const ErasedArgs &, hipStream_t);
+extern template hipError_t launch_product_gad_mid_of<FieldM32>(int, const ErasedArgs &, hipStream_t);
+extern template hipError_t launch_product_gad_mid_of<FieldM64>(int, const ErasedArgs &, hipStream_t);
+hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s);  // misc_kernels.hip: by a.field, a.gad_levels, a.in2_prepared, a.dot_terms and a.mv_outs
 
 #if defined(NTT_EXPERIMENT)
 // Tools-side experiment, NOT part of libntt_hip.so (tools/fused_gl16.hip, libntt_hip_exp.so only):
@@ -91,6 +100,11 @@ hipError_t launch_dot_rows(const FieldParams &fp, void *a, const void *bhat, int
 // both.  ONE launch: the sums of ntt_polymul_matvec_pre at the sizes without a fused middle
 hipError_t launch_matvec_rows(const FieldParams &fp, const void *a, const void *bhat, void *out, int n, size_t batch, size_t bhat_rows, size_t terms, size_t outs,
                               uint64_t scale2, hipStream_t s);
+// digits[q][k][r][i] = digit_k(a[q][r][i]) (pass.h: gadget_digit), k < levels: a is [polys][batch][2^n] canonical words, read only; digits is
+// [polys][levels][batch][2^n] words, apart from a.  The decomposition of ntt_gadget_decompose, and of ntt_polymul_gadget_pre where the
+// middle launch does not decompose.  Needs p alone, no table
+hipError_t launch_gadget_decompose(const FieldParams &fp, const void *a, void *digits, int n, size_t polys, size_t batch, int log_base, int levels, int low_bits,
+                                   hipStream_t s);
 // device-side table generation (no host upload): T[i] = base^e_kind(i), table form
 hipError_t launch_gen_table(const FieldParams &fp, void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, hipStream_t s);
 // coset vector of ntt_plan_set_coset: s[i] = shift^bitrev_logn(i mod 2^logn), table form, i < len (len = max(2^logn, 4));

@@ -89,6 +89,12 @@ struct ErasedArgs {
     int mv_outs;
     uint64_t mv_in2_stride;
     uint64_t mv_out_stride;
+    // product_mid launch of ntt_polymul_gadget_pre (the digit variants of the two summed kernels): gad_levels > 0.  `in` is then
+    // [dot_terms / gad_levels][batch][N] canonical words that are decomposed in registers: term t is digit_{t % gad_levels} of
+    // polynomial t / gad_levels (pass.h: gadget_digit); dot_* and mv_* as above.  All zero: every other launch
+    int gad_log_base;
+    int gad_levels;
+    int gad_low_bits;
 #if defined(NTT_PHASE_STAMPS)
     void *stamps;            // diagnostic build: PassArgs::stamps / stamp_records (ntt_stamps_set)
     uint32_t stamp_records;
@@ -255,6 +261,7 @@ bool fill_pass_args(const ErasedArgs &e, const PassGeom &g, PassArgs<Cfg> &a) {
     a.in2 = (const W *) e.in2;
     a.pw_scale = (W) e.pw_scale;
     a.skip_if = (const uint32_t *) e.skip_if;
+    if (e.gad_levels != 0 || e.gad_log_base != 0 || e.gad_low_bits != 0) return false;  // digit parameters: the gadget middle kernels only
     // the fused expansion runs in its own kernels and nowhere else (never beside LDS-DMA or the register prefetch: PassCfg::LDE)
     if ((e.lde_beta != 0) != Cfg::LDE) return false;
     if constexpr (Cfg::LDE) {
@@ -361,9 +368,10 @@ inline bool product_dot_used(const FieldParams &fp, int log_m) {
 }
 
 // what a launch of the summed middle (run_product_dot_pass) must carry: shared by the GPU launcher and the host model
+inline bool product_no_digits(const ErasedArgs &e) { return e.gad_levels == 0 && e.gad_log_base == 0 && e.gad_low_bits == 0; }
 inline bool product_dot_args_ok(const ErasedArgs &e) {
     const uint64_t row = (uint64_t) 1 << e.n;
-    return e.dot_terms > 0 && e.in2_prepared && e.dot_in_stride == (uint64_t) e.batch * row && e.dot_in2_stride == (e.in2_broadcast ? row : (uint64_t) e.batch * row);
+    return product_no_digits(e) && e.dot_terms > 0 && e.in2_prepared && e.dot_in_stride == (uint64_t) e.batch * row && e.dot_in2_stride == (e.in2_broadcast ? row : (uint64_t) e.batch * row);
 }
 
 // The two-output summed middle of ntt_polymul_matvec_pre (pass.h: run_product_mv_pass): which units of product_dot_dispatch have such a
@@ -402,6 +410,47 @@ inline bool product_mv_used(const FieldParams &fp, int log_m) {
 inline bool product_mv_args_ok(const ErasedArgs &e) {
     return product_dot_args_ok(e) && e.mv_outs == 2 && e.mv_in2_stride == (uint64_t) e.dot_terms * e.dot_in2_stride &&
            e.mv_out_stride == (uint64_t) e.batch << e.n;
+}
+
+// The digit variants of the two summed middle kernels (ntt_polymul_gadget_pre; pass.h: run_product_dot_pass / run_product_mv_pass with
+// GAD): which units of product_dot_dispatch have them.  Every unit compiles without scratch under its family's launch bound (register
+// table: DESIGN.md section 3.2); one that did not would be excluded here and take the decomposition kernel and the unfused digits, as the
+// two units without a summed kernel do.  The two-output digit variant is used exactly where product_mv_unit allows the two-output kernel.
+// The A/B rule -- the fused call faster than decomposition kernel + ntt_polymul_matvec_pre in EVERY burst at EVERY shape of the class
+// (profiles/polymul_gadget_ab.txt) -- held for the general 64-bit modulus (0.95-0.99x) and failed for Goldilocks (0.96-0.99x in the
+// medians, but bursts overlap at three of six shapes) and for 4-byte words (1.09-1.15x at 2^10 and 2^11: slower), so the product library
+// uses the digit kernels for the general 64-bit modulus only.  The experiment build keeps all of them, so that
+// tools/bench_polymul_gadget.py can measure them again; the host model compiled as the experiment build steps them
+// (tests/emu_product_gadget_lib.py: lib(experiment=True)).
+template <class F>
+constexpr bool product_gadget_unit(int log_m) {
+#if !defined(NTT_EXPERIMENT)
+    if (!std::is_same<F, FieldM64>::value) return false;
+#endif
+    return product_dot_unit<F>(log_m);
+}
+template <class F, class Fn>
+bool product_gadget_dispatch(int log_m, Fn &&fn) {
+    bool found = false;
+    product_dispatch<F>(log_m, [&](auto tag) {
+        if constexpr (product_gadget_unit<F>(decltype(tag)::Cfg::CI::LOG_M)) {
+            fn(tag);
+            found = true;
+        }
+    });
+    return found;
+}
+inline bool product_gadget_used(const FieldParams &fp, int log_m) {
+    return product_dot_used(fp, log_m) && with_field(fp, [&](auto f) { return product_gadget_unit<decltype(f)>(log_m); });
+}
+
+// what a launch of a digit kernel must carry: a summed launch (or a two-output one) over dot_terms = polys * gad_levels terms, and
+// digit parameters that obey the argument rule
+inline bool product_gadget_args_ok(const ErasedArgs &e) {
+    if (e.gad_levels <= 0 || e.dot_terms <= 0 || e.dot_terms % e.gad_levels != 0 || !gadget_params_ok(e.field.p, e.gad_log_base, e.gad_levels, e.gad_low_bits)) return false;
+    ErasedArgs plain = e;
+    plain.gad_log_base = plain.gad_levels = plain.gad_low_bits = 0;
+    return e.mv_outs != 0 ? product_mv_args_ok(plain) : product_dot_args_ok(plain);
 }
 
 // one leg of the product launch: the inverse pass of an operand (in, no out) or the forward pass of the product (out, no in)

@@ -305,6 +305,33 @@ __global__ __launch_bounds__(256) void matvec_rows_kernel(const typename F::W *a
     }
 }
 
+// The balanced gadget decomposition (ntt_gadget_decompose; pass.h: gadget_digit has the definition): digits[q][k][.] = digit_k(a[q][.]) for
+// every k < levels.  The field is data: the modulus alone, no Montgomery constant, no table.  blockIdx.y is the polynomial q; within its
+// [batch][N] block of `block` words one thread per 16-byte chunk, grid-stride, each word read once and its `levels` digits written to
+// the blocks (q * levels + k) of digits; a block that is no whole number of chunks goes word by word.
+template <class W>
+__global__ __launch_bounds__(256) void gadget_decompose_kernel(const W *a, W *digits, size_t block, uint64_t p, int log_base, int levels, int low_bits) {
+    constexpr int V = 16 / sizeof(W);
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    const GadgetConsts g = gadget_consts(p, GadgetParams{log_base, levels, low_bits});
+    a += (size_t) blockIdx.y * block;
+    digits += (size_t) blockIdx.y * (size_t) levels * block;
+    const size_t chunks = block % V == 0 ? block / V : 0, stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t c = (size_t) blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += stride) {
+        const Vec<W, V> x = *(reinterpret_cast<const Vec<W, V> *>(a) + c);
+        for (int k = 0; k < levels; ++k) {
+            Vec<W, V> d;
+#pragma unroll
+            for (int e = 0; e < V; ++e) d.v[e] = (W) gadget_digit(g, (uint64_t) x.v[e], k * log_base, k == levels - 1);
+            u32x4 dd;
+            __builtin_memcpy(&dd, &d, 16);
+            __builtin_nontemporal_store(dd, reinterpret_cast<u32x4 *>(digits + (size_t) k * block) + c);
+        }
+    }
+    for (size_t i = chunks * V + (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < block; i += stride)
+        for (int k = 0; k < levels; ++k) digits[(size_t) k * block + i] = (W) gadget_digit(g, (uint64_t) a[i], k * log_base, k == levels - 1);
+}
+
 // out[i] = T[i] * c, both in table (Montgomery) form: the scaled stage-0 twiddles of the inverse transform (pass.h: fold_scale)
 template <class F>
 __global__ __launch_bounds__(256) void scale_table_kernel(const typename F::W *T, typename F::W *out, size_t count,
@@ -350,6 +377,7 @@ hipError_t launch_mat_pass(bool inverse, int log_m, const ErasedArgs &a, hipStre
 
 hipError_t launch_product_mid(int log_m, const ErasedArgs &a, hipStream_t s) {
     return with_field(a.field, [&](auto f) {
+        if (!product_no_digits(a)) return launch_product_gad_mid_of<decltype(f)>(log_m, a, s);
         if (a.mv_outs != 0) return launch_product_mv_mid_of<decltype(f)>(log_m, a, s);
         if (a.dot_terms != 0) return launch_product_dot_mid_of<decltype(f)>(log_m, a, s);
         return a.in2_prepared ? launch_product_pre_mid_of<decltype(f)>(log_m, a, s) : launch_product_mid_of<decltype(f)>(log_m, a, s);
@@ -409,6 +437,26 @@ hipError_t launch_matvec_rows(const FieldParams &fp, const void *a, const void *
         }
         return hipSuccess;
     });
+}
+
+hipError_t launch_gadget_decompose(const FieldParams &fp, const void *a, void *digits, int n, size_t polys, size_t batch, int log_base, int levels, int low_bits,
+                                   hipStream_t s) {
+    const size_t block = batch << n;
+    if (block == 0 || polys == 0) return hipSuccess;
+    if (!gadget_params_ok(fp.p, log_base, levels, low_bits)) return hipErrorInvalidValue;
+    auto go = [&](auto w) {
+        using W = decltype(w);
+        // blockIdx.y is the polynomial: one launch up to 65535 polynomials, a slice per 65535 beyond
+        for (size_t q = 0; q < polys; q += 65535u) {
+            const size_t nq = polys - q < 65535u ? polys - q : 65535u;
+            hipLaunchKernelGGL(gadget_decompose_kernel<W>, dim3(grid_for((block + 16 / sizeof(W) - 1) / (16 / sizeof(W))), (unsigned) nq), dim3(256), 0, s,
+                               (const W *) a + q * block, (W *) digits + q * (size_t) levels * block, block, fp.p, log_base, levels, low_bits);
+            const hipError_t err = hipGetLastError();
+            if (err != hipSuccess) return err;
+        }
+        return hipSuccess;
+    };
+    return field_word_bytes(fp) == 4 ? go(uint32_t{}) : go(uint64_t{});
 }
 
 hipError_t launch_gen_table(const FieldParams &fp, void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, hipStream_t s) {

@@ -336,6 +336,7 @@ int ntt_plan_create(ntt_plan_t *out, int logn, uint64_t p, int word_bytes, int d
     if (const char *e = getenv("NTT_LDE_UNFUSED")) pl->lde_unfused = atoi(e) != 0;  // tools/bench_lde.py: leg B
     if (const char *e = getenv("NTT_COSET_INV_UNFUSED")) pl->cinv_unfused = atoi(e) != 0;  // tools/bench_coset_inverse.py: leg B
     if (const char *e = getenv("NTT_MATVEC_SINGLE")) pl->mv_single = atoi(e) != 0;  // tools/bench_polymul_matvec.py: leg C
+    if (const char *e = getenv("NTT_GADGET_UNFUSED")) pl->gadget_unfused = atoi(e) != 0;  // tools/bench_polymul_gadget.py: the decomposition kernel at every size
     if (const char *e = getenv("NTT_PLAN_SPLIT")) {  // "8,6,6" = CONTIG 8 stages + two 6-stage column passes
         std::vector<PassDesc> v;
         int s0 = 0;
@@ -501,6 +502,9 @@ int64_t ntt_plan_info(ntt_plan_t pl, int what) NTT_GUARD {
             const std::vector<PassDesc> &passes = passes_for(pl, 1);
             return ntt::polymul_dot_fused(*pl, passes, 1) && ntt::polymul_matvec_paired(*pl, passes) ? 1 : 0;
         }
+        case 15: {  // does ntt_polymul_gadget_pre decompose inside the middle launch (the pinned decomposition, or the one of a small batch)
+            return ntt::polymul_gadget_fused(*pl, passes_for(pl, 1), 1) ? 1 : 0;
+        }
         case 8: {  // capacity for ntt_forward_profile whatever the batch
             size_t k = 0;
             for (const PlanAlt &a : pl->alts) k = a.passes.size() > k ? a.passes.size() : k;
@@ -644,6 +648,7 @@ int ntt_plan_clone(ntt_plan_t src, int device, ntt_plan_t *out) NTT_GUARD {
     }
     pl->cinv_unfused = src->cinv_unfused;
     pl->mv_single = src->mv_single;
+    pl->gadget_unfused = src->gadget_unfused;
     if (src->cinv_set) {  // ... and the coset-interpolation setting with its vector
         const size_t bytes = cinv_u_words(src) * (size_t) src->word_bytes;
         DeviceGuard g(device);
@@ -947,6 +952,76 @@ int ntt_polymul_matvec_pre(ntt_plan_t pl, void *d_a, const void *d_bhat, size_t 
         [&](void *buf, const void *hat, void *out) {
             RoctxRange sum("product(matvec): row sums");
             return (int) ntt::launch_matvec_rows(pl->field, buf, hat, out, pl->logn, batch, bhat_rows, terms, outs, ntt::pw_scale_form(*pl, pl->ninv_plain), s);
+        });
+} NTT_GUARD_END
+
+int ntt_gadget_decompose(ntt_plan_t pl, const void *d_a, size_t polys, size_t batch, int log_base, int levels, int low_bits, void *d_digits,
+                         void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_a, d_digits, batch);
+    if (rc) return rc;
+    if (batch == 0) return NTT_OK;
+    if (!ntt::gadget_params_ok(pl->p, log_base, levels, low_bits)) return NTT_E_ARG;
+    if (polys == 0 || polys > 0x7FFFFFFFull / batch / (size_t) levels) return NTT_E_ARG;  // the digits are polys * levels * batch rows of a product
+    {
+        using u128 = unsigned __int128;
+        const u128 row = table_bytes(pl), top = (u128) 1 << 63;
+        const u128 a0 = (uintptr_t) d_a, a1 = a0 + (u128) polys * batch * row, g0 = (uintptr_t) d_digits, g1 = g0 + (u128) polys * (u128) levels * batch * row;
+        if (a1 > top || g1 > top || (a0 < g1 && g0 < a1)) return NTT_E_ARG;
+    }
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    RoctxRange whole("ntt_gadget_decompose");
+    return (int) ntt::launch_gadget_decompose(pl->field, d_a, d_digits, pl->logn, polys, batch, log_base, levels, low_bits, (hipStream_t) stream);
+} NTT_GUARD_END
+
+int ntt_polymul_gadget_pre(ntt_plan_t pl, const void *d_a, size_t polys, int log_base, int levels, int low_bits, void *d_work, const void *d_bhat, size_t bhat_rows,
+                           size_t outs, void *d_out, size_t batch, void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_a, d_bhat, batch);
+    if (rc) return rc;
+    if (batch && (!d_out || ((uintptr_t) d_out & 15u) || !d_work || ((uintptr_t) d_work & 15u))) return NTT_E_ARG;
+    if (batch && bhat_rows != 1 && bhat_rows != batch) return NTT_E_ARG;
+    if (batch && !ntt::gadget_params_ok(pl->p, log_base, levels, low_bits)) return NTT_E_ARG;
+    if (batch && (polys == 0 || polys > 0x7FFFFFFFull / batch / (size_t) levels)) return NTT_E_ARG;  // terms * batch rows, terms = polys * levels
+    if (batch && (outs == 0 || outs > 0x7FFFFFFFull / batch)) return NTT_E_ARG;                      // the forward passes over outs * batch rows
+    if (!pl->has_table) return NTT_E_NOTABLE;
+    if (!pl->has_inv) return NTT_E_NOTINVERTIBLE;
+    if (batch == 0) return NTT_OK;
+    const size_t terms = polys * (size_t) levels;
+    {
+        using u128 = unsigned __int128;
+        const u128 row = table_bytes(pl), top = (u128) 1 << 63;  // no buffer ends beyond that: four ranges that cannot wrap
+        const u128 lo[4] = {(uintptr_t) d_a, (uintptr_t) d_work, (uintptr_t) d_bhat, (uintptr_t) d_out};
+        const u128 hi[4] = {lo[0] + (u128) polys * batch * row, lo[1] + (u128) terms * batch * row, lo[2] + (u128) outs * terms * bhat_rows * row,
+                            lo[3] + (u128) outs * batch * row};
+        for (int i = 0; i < 4; ++i) {
+            if (hi[i] > top) return NTT_E_ARG;
+            for (int j = 0; j < i; ++j)
+                if (lo[i] < hi[j] && lo[j] < hi[i]) return NTT_E_ARG;  // pairwise disjoint
+        }
+    }
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    hipStream_t s = (hipStream_t) stream;
+    RoctxRange whole("ntt_polymul_gadget_pre");
+    const std::vector<PassDesc> &passes = passes_for(pl, batch);  // by batch, as ntt_polymul_matvec_pre selects it
+    return ntt::seq_polymul_gadget(
+        *pl, passes, d_a, polys, log_base, levels, low_bits, d_work, d_bhat, bhat_rows, outs, d_out, batch,
+        [&](const ntt::Step &st) {
+            return launch_step(st.family == ntt::STEP_PRODUCT
+                                   ? (st.args.gad_levels ? (st.args.mv_outs ? "product(gadget): fused middle with digits, two outputs" : "product(gadget): fused middle with digits")
+                                      : st.args.mv_outs  ? "product(gadget): fused middle, two outputs"
+                                                         : "product(gadget): fused middle")
+                               : st.inverse ? "product(gadget): inv pass"
+                                            : "product(gadget): fwd pass",
+                               st, s);
+        },
+        [&](void *buf, const void *hat, void *out) {
+            RoctxRange sum("product(gadget): row sums");
+            return (int) ntt::launch_matvec_rows(pl->field, buf, hat, out, pl->logn, batch, bhat_rows, terms, outs, ntt::pw_scale_form(*pl, pl->ninv_plain), s);
+        },
+        [&](const void *src, void *digits) {
+            RoctxRange dec("product(gadget): decomposition");
+            return (int) ntt::launch_gadget_decompose(pl->field, src, digits, pl->logn, polys, batch, log_base, levels, low_bits, s);
         });
 } NTT_GUARD_END
 

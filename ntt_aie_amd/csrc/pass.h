@@ -1929,6 +1929,57 @@ NTT_HD void phase_pre_mac(const Ctx<Cfg> &c, const PassArgs<Cfg> &a, const typen
 #endif
 }
 
+// ---- balanced gadget decomposition (ntt_gadget_decompose, ntt_polymul_gadget_pre) ------------------------------------------------
+// digit_k(a) of a canonical word a, k < levels, as include/ntt_hip.h defines it: centred magnitude m = min(a, p - a) with its sign,
+// u = round-half-away(m / 2^low_bits), v = u + bias with bias = sum_{k < levels - 1} 2^(k w + w - 1), w = log_base; the lower
+// levels - 1 digits are ((v >> k w) & (B - 1)) - B/2 in [-B/2, B/2), the top one v >> (levels - 1) w, unmasked and non-negative; the
+// digit is sign(a) * e_k mod p.  Under the argument rule (gadget_params_ok) v fits 64 unsigned bits and every |e_k| is below p, so
+// the 64-bit steps below are the integer arithmetic of the definition, for every word class.  Written once: the decomposition kernel
+// (misc_kernels.hip), the digit variants of the summed middle kernels (below) and the host model run these lines.
+struct GadgetParams {  // levels == 0: no decomposition
+    int log_base, levels, low_bits;
+};
+struct GadgetConsts {
+    uint64_t p, half, h, bias, mask, half_b;
+    int log_base, low_bits;
+};
+NTT_HD GadgetConsts gadget_consts(uint64_t p, const GadgetParams &gp) {
+    GadgetConsts g;
+    g.p = p;
+    g.half = (p - 1) >> 1;
+    g.h = gp.low_bits > 0 ? (uint64_t) 1 << (gp.low_bits - 1) : 0;
+    g.bias = 0;
+    for (int k = 0; k + 1 < gp.levels; ++k) g.bias += (uint64_t) 1 << (k * gp.log_base + gp.log_base - 1);
+    g.mask = ((uint64_t) 1 << gp.log_base) - 1;
+    g.half_b = (uint64_t) 1 << (gp.log_base - 1);
+    g.log_base = gp.log_base;
+    g.low_bits = gp.low_bits;
+    return g;
+}
+// shift = k * log_base; top = (k == levels - 1)
+NTT_HD uint64_t gadget_digit(const GadgetConsts &g, uint64_t a, int shift, bool top) {
+    const bool neg = a > g.half;
+    const uint64_t m = neg ? g.p - a : a;
+    const uint64_t f = ((((m + g.h) >> g.low_bits) + g.bias) >> shift);
+    const uint64_t d = f & g.mask;
+    const bool eneg = !top && d < g.half_b;
+    const uint64_t mag = top ? f : (eneg ? g.half_b - d : d - g.half_b);
+    return (mag != 0 && neg != eneg) ? g.p - mag : mag;
+}
+// the argument rule (anything else is NTT_E_ARG)
+inline bool gadget_params_ok(uint64_t p, int log_base, int levels, int low_bits) {
+    if (log_base < 1 || log_base > 31 || levels < 1 || low_bits < 0) return false;
+    if ((uint64_t) low_bits + (uint64_t) (levels - 1) * (uint64_t) log_base > 63) return false;
+    if (!(((uint64_t) 1 << (log_base - 1)) < p)) return false;
+    const uint64_t h = low_bits > 0 ? (uint64_t) 1 << (low_bits - 1) : 0, u_max = (((p - 1) >> 1) + h) >> low_bits;
+    return (u_max >> ((levels - 1) * log_base)) + 1 < p;
+}
+template <class F>
+NTT_HD uint64_t field_modulus(const F &f) {
+    return (uint64_t) f.p;
+}
+NTT_HD uint64_t field_modulus(const FieldGL &) { return FieldGL::P; }
+
 // d_out[r] = Fwd( N^-1 . sum_{k < terms} InvU(a[k][r]) . b^[k][r | 0] ): run_product_pass<.., PRE = true> with a loop over terms
 // between "load" and "forward".  Per resident unit: zero the accumulator; per term load the unit of a[k], run the inverse rounds,
 // acc += x . b^[k] (phase_pre_mac); then cf.x = acc * pw_scale, forward rounds, store.  The product is linear in x, so the sum is
@@ -1937,14 +1988,20 @@ NTT_HD void phase_pre_mac(const Ctx<Cfg> &c, const PassArgs<Cfg> &a, const typen
 // kernel, and b^ is never held across the inverse rounds: 2 x E words live, as there.  No register prefetch of a[k + 1]: it would
 // be a third E-word array beside x and acc in kernels that sit at the 128-VGPR bound already.
 // Exec: as run_product_pass; eachIF's `keep` is the accumulator, its `pre` is not used.
-template <class CI, class CF, class Exec, int M32_MODE = -1>
-NTT_HD void run_product_dot_pass(Exec &ex, const PassArgs<CI> &aa, const typename CI::W *bhat, const PassArgs<CF> &af, bool pre_bcast, int terms) {
+// GAD (ntt_polymul_gadget_pre): the term loop decomposes on the fly.  a is [terms / levels][batch][N] canonical words; term t loads its
+// unit from polynomial t / levels and, between the load and the first inverse round, replaces the thread's E words by digit_{t % levels}
+// of themselves (gadget_digit, in registers).  The unit is loaded again for every level -- a further E-word array of raw words does not
+// fit the register bound, and the re-reads of at most 32 KB come from cache.  Everything after that is the kernel above word for word.
+template <class CI, class CF, class Exec, int M32_MODE = -1, bool GAD = false>
+NTT_HD void run_product_dot_pass(Exec &ex, const PassArgs<CI> &aa, const typename CI::W *bhat, const PassArgs<CF> &af, bool pre_bcast, int terms,
+                                 const GadgetParams gp = GadgetParams{0, 0, 0}) {
     using W = typename CI::W;
     static_assert(CI::CONTIG && CF::CONTIG && CI::INV && !CF::INV, "middle of the product: inverse CONTIG then forward CONTIG");
     static_assert(CI::LOG_M == CF::LOG_M && CI::LOG_E == CF::LOG_E && CI::LOG_NT == CF::LOG_NT && CI::R == CF::R, "same tile");
     static_assert(CI::DIRECT_LOAD && CF::DIRECT_STORE && !CF::DMA && CI::R > 1, "register <-> HBM at both ends");
     constexpr int R = CI::R;
     using WL = std::integral_constant<bool, CI::WAVE_LOCAL>;
+    [[maybe_unused]] const GadgetConsts gc = GAD ? gadget_consts(field_modulus(aa.field), gp) : GadgetConsts{};  // wave-uniform
     ex.init(aa, af);
     static_for<0, R>([&](auto rr) {  // fill the LDS twiddle tables (once per workgroup: its hi-block is fixed)
         constexpr int r = decltype(rr)::value;
@@ -1965,8 +2022,21 @@ NTT_HD void run_product_dot_pass(Exec &ex, const PassArgs<CI> &aa, const typenam
         const size_t a_stride = (size_t) aa.batch << aa.n, b_stride = pre_bcast ? (size_t) 1 << aa.n : a_stride;
         PassArgs<CI> ak = aa;
         const W *bk = bhat;
-        for (int k = 0; k < terms; ++k, ak.in += a_stride, bk += b_stride) {
+        [[maybe_unused]] int lev = 0;  // GAD: the level of term k
+        for (int k = 0; k < terms; ++k, ak.in += GAD ? (size_t) 0 : a_stride, bk += b_stride) {
             ex.eachI([&](Ctx<CI> &c) { phase_load_direct_to<CI, R - 1>(c, ak, it, c.x, c.active); });
+            if constexpr (GAD) {
+                const int shift = lev * gp.log_base;
+                const bool top = lev == gp.levels - 1;
+                ex.eachI([&](Ctx<CI> &c) {
+#pragma unroll
+                    for (int e = 0; e < CI::E; ++e) c.x[e] = (W) gadget_digit(gc, (uint64_t) c.x[e], shift, top);
+                });
+                if (++lev == gp.levels) {  // the next term is level 0 of the next polynomial
+                    lev = 0;
+                    ak.in += a_stride;
+                }
+            }
             // A barrier per term boundary, the one the two-operand kernel has between its two inverse units: term k - 1 ended with
             // every thread reading its round-0 words (phase_lds_read<CI, 0>), and this term begins by writing the round R - 1
             // positions, which belong to other threads -- other waves may still be reading.  (Neither "no barrier here" argument
@@ -2020,15 +2090,17 @@ NTT_HD void run_product_dot_pass(Exec &ex, const PassArgs<CI> &aa, const typenam
 // Three E-word arrays are live in the term loop (x and both accumulators): the kernel is built under a register bound of its own
 // (product_kernel.inc: NTT_PRODUCT_MV_WPE).
 // Exec: as run_product_pass; eachIF's `keep` and `pre` are the two accumulators.
-template <class CI, class CF, class Exec, int M32_MODE = -1>
+// GAD: the digit variant, as in run_product_dot_pass -- the same two changes of the term loop.
+template <class CI, class CF, class Exec, int M32_MODE = -1, bool GAD = false>
 NTT_HD void run_product_mv_pass(Exec &ex, const PassArgs<CI> &aa, const typename CI::W *bhat, const PassArgs<CF> &af, bool pre_bcast, int terms, size_t b_out_stride,
-                                size_t o_out_stride) {
+                                size_t o_out_stride, const GadgetParams gp = GadgetParams{0, 0, 0}) {
     using W = typename CI::W;
     static_assert(CI::CONTIG && CF::CONTIG && CI::INV && !CF::INV, "middle of the product: inverse CONTIG then forward CONTIG");
     static_assert(CI::LOG_M == CF::LOG_M && CI::LOG_E == CF::LOG_E && CI::LOG_NT == CF::LOG_NT && CI::R == CF::R, "same tile");
     static_assert(CI::DIRECT_LOAD && CF::DIRECT_STORE && !CF::DMA && CI::R > 1, "register <-> HBM at both ends");
     constexpr int R = CI::R;
     using WL = std::integral_constant<bool, CI::WAVE_LOCAL>;
+    [[maybe_unused]] const GadgetConsts gc = GAD ? gadget_consts(field_modulus(aa.field), gp) : GadgetConsts{};  // wave-uniform
     ex.init(aa, af);
     static_for<0, R>([&](auto rr) {  // fill the LDS twiddle tables (once per workgroup: its hi-block is fixed)
         constexpr int r = decltype(rr)::value;
@@ -2050,8 +2122,21 @@ NTT_HD void run_product_mv_pass(Exec &ex, const PassArgs<CI> &aa, const typename
         const size_t a_stride = (size_t) aa.batch << aa.n, b_stride = pre_bcast ? (size_t) 1 << aa.n : a_stride;
         PassArgs<CI> ak = aa;
         const W *bk = bhat;
-        for (int k = 0; k < terms; ++k, ak.in += a_stride, bk += b_stride) {
+        [[maybe_unused]] int lev = 0;  // GAD: the level of term k
+        for (int k = 0; k < terms; ++k, ak.in += GAD ? (size_t) 0 : a_stride, bk += b_stride) {
             ex.eachI([&](Ctx<CI> &c) { phase_load_direct_to<CI, R - 1>(c, ak, it, c.x, c.active); });
+            if constexpr (GAD) {
+                const int shift = lev * gp.log_base;
+                const bool top = lev == gp.levels - 1;
+                ex.eachI([&](Ctx<CI> &c) {
+#pragma unroll
+                    for (int e = 0; e < CI::E; ++e) c.x[e] = (W) gadget_digit(gc, (uint64_t) c.x[e], shift, top);
+                });
+                if (++lev == gp.levels) {  // the next term is level 0 of the next polynomial
+                    lev = 0;
+                    ak.in += a_stride;
+                }
+            }
             // the barrier per term boundary of run_product_dot_pass; for k == 0 the edge is the one from the previous unit (below)
             if (k > 0) ex.sync(WL{});
             static_for<0, R>([&](auto kk) {

@@ -4,7 +4,8 @@
 // (run_product_pass<.., PRE = true>, ntt_polymul_negacyclic_pre), and by the three kernels_<field>_product_dot.hip ones, which define
 // NTT_PRODUCT_DOT: that middle summed over the terms of an inner product (run_product_dot_pass, ntt_polymul_dot_pre), and by the three
 // kernels_<field>_product_mv.hip ones, which define NTT_PRODUCT_MV: the summed middle for two outputs at once (run_product_mv_pass,
-// ntt_polymul_matvec_pre).
+// ntt_polymul_matvec_pre), and by the three kernels_<field>_product_gad.hip ones, which define NTT_PRODUCT_GAD: the digit variants of
+// the last two (GAD = true: the balanced gadget decomposition in registers, ntt_polymul_gadget_pre).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -137,11 +138,53 @@ void product_mv_kernel(PassArgs<CI> aa, const typename CI::W *bhat, int bcast, i
     }
 }
 
+// ... the digit variants (ntt_polymul_gadget_pre): a is [terms / levels][batch][N] canonical words, decomposed in registers; the three
+// digit parameters travel as kernel arguments.  Each under the launch bound of the kernel it is a variant of
+template <class CI, class CF>
+__global__ __launch_bounds__(CI::NT, NTT_PRODUCT_WPE)
+void product_dot_gad_kernel(PassArgs<CI> aa, const typename CI::W *bhat, int bcast, int terms, int log_base, int levels, int low_bits, PassArgs<CF> af) {
+    __shared__ __attribute__((aligned(16))) typename CI::W tile[CI::LDS_WORDS];
+    __shared__ __attribute__((aligned(16))) typename CI::W tab_i[tw_table_words<CI>()];
+    __shared__ __attribute__((aligned(16))) typename CI::W tab_f[tw_table_words<CF>()];
+    GpuProductExec<CI, CF> ex;
+    ex.tile = tile;
+    ex.tab_i = tab_i;
+    ex.tab_f = tab_f;
+    const GadgetParams gp{log_base, levels, low_bits};
+    if constexpr (std::is_same<typename CI::F, FieldM32>::value) {
+        if (aa.field.p < 0x40000000u) run_product_dot_pass<CI, CF, GpuProductExec<CI, CF>, 0, true>(ex, aa, bhat, af, bcast != 0, terms, gp);
+        else if (aa.field.p < 0x80000000u) run_product_dot_pass<CI, CF, GpuProductExec<CI, CF>, 1, true>(ex, aa, bhat, af, bcast != 0, terms, gp);
+        else run_product_dot_pass<CI, CF, GpuProductExec<CI, CF>, 2, true>(ex, aa, bhat, af, bcast != 0, terms, gp);
+    } else {
+        run_product_dot_pass<CI, CF, GpuProductExec<CI, CF>, -1, true>(ex, aa, bhat, af, bcast != 0, terms, gp);
+    }
+}
+template <class CI, class CF>
+__global__ __launch_bounds__(CI::NT, NTT_PRODUCT_MV_WPE)
+void product_mv_gad_kernel(PassArgs<CI> aa, const typename CI::W *bhat, int bcast, int terms, size_t b_out_stride, size_t o_out_stride, int log_base, int levels,
+                           int low_bits, PassArgs<CF> af) {
+    __shared__ __attribute__((aligned(16))) typename CI::W tile[CI::LDS_WORDS];
+    __shared__ __attribute__((aligned(16))) typename CI::W tab_i[tw_table_words<CI>()];
+    __shared__ __attribute__((aligned(16))) typename CI::W tab_f[tw_table_words<CF>()];
+    GpuProductExec<CI, CF> ex;
+    ex.tile = tile;
+    ex.tab_i = tab_i;
+    ex.tab_f = tab_f;
+    const GadgetParams gp{log_base, levels, low_bits};
+    if constexpr (std::is_same<typename CI::F, FieldM32>::value) {
+        if (aa.field.p < 0x40000000u) run_product_mv_pass<CI, CF, GpuProductExec<CI, CF>, 0, true>(ex, aa, bhat, af, bcast != 0, terms, b_out_stride, o_out_stride, gp);
+        else if (aa.field.p < 0x80000000u) run_product_mv_pass<CI, CF, GpuProductExec<CI, CF>, 1, true>(ex, aa, bhat, af, bcast != 0, terms, b_out_stride, o_out_stride, gp);
+        else run_product_mv_pass<CI, CF, GpuProductExec<CI, CF>, 2, true>(ex, aa, bhat, af, bcast != 0, terms, b_out_stride, o_out_stride, gp);
+    } else {
+        run_product_mv_pass<CI, CF, GpuProductExec<CI, CF>, -1, true>(ex, aa, bhat, af, bcast != 0, terms, b_out_stride, o_out_stride, gp);
+    }
+}
+
 template <class PC, bool PRE>
 hipError_t launch_product(const ErasedArgs &e, hipStream_t s) {
     using CI = typename PC::CI;
     using CF = typename PC::CF;
-    if ((e.in2_prepared != 0) != PRE || (!PRE && e.in2_broadcast) || e.dot_terms != 0) return hipErrorInvalidValue;  // each kernel family runs its own launches only
+    if ((e.in2_prepared != 0) != PRE || (!PRE && e.in2_broadcast) || e.dot_terms != 0 || !product_no_digits(e)) return hipErrorInvalidValue;  // each kernel family runs its own launches only
     const PassGeom g = product_geometry<PC>(e.n, e.batch, e.target_wgs);
     if (g.grid_y == 0) return hipSuccess;
     if (g.grid_y > 65535u) return hipErrorInvalidValue;  // callers fall back to the separate passes (launch.h: product_mid_fits)
@@ -187,10 +230,44 @@ hipError_t launch_product_mv(const ErasedArgs &e, hipStream_t s) {
     return hipGetLastError();
 }
 
+// the digit variants: a summed launch, or -- e.mv_outs == 2, only where the unit has a two-output kernel -- a two-output one
+template <class PC>
+hipError_t launch_product_gad(const ErasedArgs &e, hipStream_t s) {
+    using CI = typename PC::CI;
+    using CF = typename PC::CF;
+    using F = typename CI::F;
+    if (!product_gadget_args_ok(e)) return hipErrorInvalidValue;
+    const PassGeom g = product_geometry<PC>(e.n, e.batch, e.target_wgs);
+    if (g.grid_y == 0) return hipSuccess;
+    if (g.grid_y > 65535u) return hipErrorInvalidValue;  // callers fall back to the separate passes (launch.h: product_mid_fits)
+    PassArgs<CI> aa;
+    PassArgs<CF> af;
+    fill_product_args<PC>(e, g, aa, af);
+    if (e.mv_outs != 0) {
+        if constexpr (product_mv_unit<F>(CI::LOG_M))
+            hipLaunchKernelGGL((product_mv_gad_kernel<CI, CF>), dim3(g.grid_x, g.grid_y, 1), dim3(CI::NT, 1, 1), 0, s, aa, (const typename CI::W *) e.in2, e.in2_broadcast,
+                               e.dot_terms, (size_t) e.mv_in2_stride, (size_t) e.mv_out_stride, e.gad_log_base, e.gad_levels, e.gad_low_bits, af);
+        else
+            return hipErrorInvalidValue;
+    } else {
+        hipLaunchKernelGGL((product_dot_gad_kernel<CI, CF>), dim3(g.grid_x, g.grid_y, 1), dim3(CI::NT, 1, 1), 0, s, aa, (const typename CI::W *) e.in2, e.in2_broadcast,
+                           e.dot_terms, e.gad_log_base, e.gad_levels, e.gad_low_bits, af);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace
 
 // every unit size with a kernel (launch.h: product_dispatch); instantiated for this unit's field only, as launch_pass_of is (kernels.h)
-#if defined(NTT_PRODUCT_MV)
+#if defined(NTT_PRODUCT_GAD)
+template <class F>
+hipError_t launch_product_gad_mid_of(int log_m, const ErasedArgs &a, hipStream_t s) {
+    hipError_t err = hipErrorInvalidValue;
+    product_gadget_dispatch<F>(log_m, [&](auto tag) { err = launch_product_gad<typename decltype(tag)::Cfg>(a, s); });
+    return err;
+}
+template hipError_t launch_product_gad_mid_of<NTT_FIELD>(int, const ErasedArgs &, hipStream_t);
+#elif defined(NTT_PRODUCT_MV)
 template <class F>
 hipError_t launch_product_mv_mid_of(int log_m, const ErasedArgs &a, hipStream_t s) {
     hipError_t err = hipErrorInvalidValue;

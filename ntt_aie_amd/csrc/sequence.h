@@ -45,6 +45,7 @@ struct PlanFacts {
     int lde_unfused = 0;     // NTT_LDE_UNFUSED=1: ntt_lde takes the separate expansion kernel at every size
     int cinv_unfused = 0;    // NTT_COSET_INV_UNFUSED=1: ntt_coset_inverse takes the separate row-scaling kernel at every size
     int mv_single = 0;       // NTT_MATVEC_SINGLE=1: ntt_polymul_matvec_pre runs one summed middle launch per output, no two-output kernel
+    int gadget_unfused = 0;  // NTT_GADGET_UNFUSED=1: ntt_polymul_gadget_pre runs the decomposition kernel and the digits' product at every size
 };
 
 #if defined(NTT_PHASE_STAMPS)
@@ -422,6 +423,44 @@ int seq_polymul_matvec(const PlanFacts &pf, const std::vector<host::PassDesc> &p
         j += two ? 2 : 1;
     }
     return seq_passes(pf, passes, 1, passes.size(), false, out, out, outs * batch, LAYOUT_NATURAL, [](ErasedArgs &, size_t) {}, emit);
+}
+
+// ntt_polymul_gadget_pre: out[j][r] = Fwd( N^-1 . sum_t InvU(digit_{t mod levels}(a[t div levels][r])) . bhat[j][t][r | 0] ), t < polys * levels,
+// j < outs: seq_polymul_matvec of the balanced gadget digits of a (pass.h: gadget_digit).  a is [polys][batch][N] canonical words and is
+// NEVER written; work is caller scratch of polys * levels * batch * N words; bhat is [outs][polys * levels][bhat_rows][N], never written;
+// out is [outs][batch][N]; the four lie apart.
+// Where polymul_gadget_fused() -- the decomposition for this batch is ONE pass, polymul_dot_fused(), and the unit has digit kernels
+// (launch.h: product_gadget_used) --: only the middle launches of seq_polymul_matvec, as digit launches (gad_*) that read a itself and
+// decompose in registers: ONE per pair of outputs where the two-output kernel is used plus a summed one for an odd last output, else one
+// per output.  No decomposition step, nothing reads or writes work.
+// Everywhere else -- a multi-pass size, a size without a fused middle, a unit without a digit kernel, a pinned alternative without a
+// middle, the experiment build's switch --: decompose(a, work), ONE launch of the decomposition kernel (kernels.h:
+// launch_gadget_decompose), then exactly seq_polymul_matvec on work.
+// Either way block j of out holds the words seq_polymul_matvec leaves for the digits: the digit launches run its kernels' code on the
+// same words in the same order.  The caller has checked the digit parameters (pass.h: gadget_params_ok), polys, outs >= 1 and
+// polys * levels * batch, outs * batch <= 2^31 - 1.
+inline bool polymul_gadget_fused(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, size_t batch) {
+    return passes.size() == 1 && polymul_dot_fused(pf, passes, batch) && product_gadget_used(pf.field, passes.front().log_m) && !pf.gadget_unfused;
+}
+template <class Emit, class MvRows, class Decompose>
+int seq_polymul_gadget(const PlanFacts &pf, const std::vector<host::PassDesc> &passes, const void *a, size_t polys, int log_base, int levels, int low_bits, void *work,
+                       const void *bhat, size_t bhat_rows, size_t outs, void *out, size_t batch, Emit &&emit, MvRows &&mv_rows, Decompose &&decompose) {
+    const size_t terms = polys * (size_t) levels;
+    if (!polymul_gadget_fused(pf, passes, batch)) {
+        if (const int rc = decompose(a, work)) return rc;
+        return seq_polymul_matvec(pf, passes, work, bhat, bhat_rows, terms, outs, out, batch, emit, mv_rows);
+    }
+    // the middle launches of seq_polymul_matvec with `a` in the place of the digits; the digit parameters ride on each
+    return seq_polymul_matvec(
+        pf, passes, const_cast<void *>(a), bhat, bhat_rows, terms, outs, out, batch,
+        [&](const Step &st) {
+            Step mid = st;
+            mid.args.gad_log_base = log_base;
+            mid.args.gad_levels = levels;
+            mid.args.gad_low_bits = low_bits;
+            return emit(mid);
+        },
+        mv_rows);
 }
 
 }  // namespace ntt

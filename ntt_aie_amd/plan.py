@@ -497,6 +497,68 @@ class NTTPlan:
                                                 self._stream(stream)), "ntt_polymul_matvec_pre")
         return out
 
+    def _operand(self, t: torch.Tensor) -> None:
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError("buffer is not on cuda:%d" % self.device)
+        if not t.is_contiguous() or t.element_size() != self.word_bytes:
+            raise ValueError("buffer must be contiguous with %d-byte words" % self.word_bytes)
+
+    def gadget_decompose(self, a: torch.Tensor, log_base: int, levels: int, low_bits: int = 0, out: torch.Tensor | None = None,
+                         stream=None) -> torch.Tensor:
+        """The balanced gadget digits of a (ntt_gadget_decompose; include/ntt_hip.h has the definition): a is [polys, batch, N] canonical
+        words and is only read; the result, [polys, levels, batch, N], viewed as [polys * levels, batch, N] is an operand of
+        polymul_dot_pre / polymul_matvec_pre.  Needs no table."""
+        if a.dim() != 3 or a.shape[2] != self.n:
+            raise ValueError("a must be [polys, batch, N]")
+        polys, rows = int(a.shape[0]), int(a.shape[1])
+        if polys == 0 or levels < 1:
+            raise ValueError("a has no polynomials" if polys == 0 else "levels must be at least 1")
+        if out is None:
+            out = torch.empty((polys, levels, rows, self.n), dtype=a.dtype, device=a.device)
+        if tuple(out.shape) != (polys, levels, rows, self.n):
+            raise ValueError("out must be [polys, levels, batch, N]")
+        self._operand(a)
+        self._operand(out)
+        check(_lib.lib().ntt_gadget_decompose(self._h, a.data_ptr(), polys, rows, log_base, levels, low_bits, out.data_ptr(), self._stream(stream)),
+              "ntt_gadget_decompose")
+        return out
+
+    def polymul_gadget_pre(self, a: torch.Tensor, log_base: int, levels: int, low_bits: int, bhat: torch.Tensor, work: torch.Tensor | None = None,
+                           out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """out[j] = sum_t digit_{t mod levels}(a[t div levels]) * b[j][t] mod (x^N + 1, p), all b[j][t] given prepared
+        (ntt_polymul_gadget_pre): polymul_matvec_pre of gadget_decompose(a), bit for bit, with the decomposition inside the middle launch
+        where the plan has such a kernel.  a is [polys, batch, N] and is NOT written; bhat is [J, polys * levels, batch, N], or
+        [J, polys * levels, N] / [J, polys * levels, 1, N] (broadcast); `work`, scratch of polys * levels * batch * N words, and `out`,
+        [J, batch, N], are allocated when not given.  The four buffers must not overlap."""
+        if a.dim() != 3 or a.shape[2] != self.n:
+            raise ValueError("a must be [polys, batch, N]")
+        polys, rows_a = int(a.shape[0]), int(a.shape[1])
+        if polys == 0 or levels < 1:
+            raise ValueError("a has no polynomials" if polys == 0 else "levels must be at least 1")
+        terms = polys * levels
+        if bhat.dim() == 4 and tuple(bhat.shape[1:]) == (terms, rows_a, self.n):
+            rows = rows_a
+        elif (bhat.dim() == 3 and tuple(bhat.shape[1:]) == (terms, self.n)) or (bhat.dim() == 4 and tuple(bhat.shape[1:]) == (terms, 1, self.n)):
+            rows = 1
+        else:
+            raise ValueError("bhat must be [outs, polys * levels, batch, N], or [outs, polys * levels, N] / [outs, polys * levels, 1, N] (broadcast)")
+        outs = int(bhat.shape[0])
+        if outs == 0:
+            raise ValueError("bhat has no outputs")
+        if work is None:
+            work = torch.empty((terms, rows_a, self.n), dtype=a.dtype, device=a.device)
+        if work.numel() != terms * rows_a * self.n:
+            raise ValueError("work must hold polys * levels * batch * N words")
+        if out is None:
+            out = torch.empty((outs, rows_a, self.n), dtype=a.dtype, device=a.device)
+        if out.dim() != 3 or tuple(out.shape) != (outs, rows_a, self.n):
+            raise ValueError("out must be [outs, batch, N]")
+        for t in (a, work, bhat, out):
+            self._operand(t)
+        check(_lib.lib().ntt_polymul_gadget_pre(self._h, a.data_ptr(), polys, log_base, levels, low_bits, work.data_ptr(), bhat.data_ptr(), rows, outs,
+                                                out.data_ptr(), rows_a, self._stream(stream)), "ntt_polymul_gadget_pre")
+        return out
+
     def count_noncanonical(self, buf: torch.Tensor) -> int:
         """How many words of `buf` are >= p (the transforms require canonical residues)."""
         b = self._batch(buf)
