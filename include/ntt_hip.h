@@ -453,6 +453,50 @@ int ntt_gadget_decompose(ntt_plan_t plan, const void *d_a, size_t polys, size_t 
 int ntt_polymul_gadget_pre(ntt_plan_t plan, const void *d_a, size_t polys, int log_base, int levels, int low_bits, void *d_work,
                            const void *d_bhat, size_t bhat_rows, size_t outs, void *d_out, size_t batch, void *stream);
 
+/* SIGNED NEGACYCLIC MAPS -- the coefficient permutations that come BEFORE the digits in the two workloads above: a blind-rotation step
+ * ACC <- ACC + bsk_i [.] (X^e_r . ACC - ACC), the exponent per row, data-dependent and already on the device, and a slot rotation
+ * a(X) -> a(X^g) followed by a gadget key switch.  Defined at word level for all three word classes from the plan's p and logn alone.
+ * N = 2^logn, M2 = 2N - 1, j < N the DESTINATION index; both maps are one rule t -> (src, neg) = (t & (N - 1), (t & N) != 0):
+ *   NTT_MAP_MONOMIAL      y = X^e . a mod (X^N + 1):  e = exp & M2 -- ANY uint32_t is legal and is taken mod 2N, so a caller's -a_i as an
+ *                         unsigned word works (2N divides 2^32) --,  t = (j - e) & M2
+ *   NTT_MAP_AUTOMORPHISM  y(X) = a(X^g), g odd, 1 <= g < 2N:  t = (j . ginv) & M2, ginv = g^-1 mod 2N computed on the host (the 32-bit
+ *                         product may wrap: harmless, logn <= 28)
+ *   value                 x = a[src];  neg and x != 0:  x = p - x
+ *   flag NTT_MAP_MINUS_IDENTITY (bit 0 of `flags`; any other bit is NTT_E_ARG):  x = x >= a[j] ? x - a[j] : x + (p - a[j])  (y - a mod p)
+ * digit_k(p - a) = -digit_k(a), so the digits of the mapped word are those of the definition above.
+ * Shared rules: d_in / d_a is [polys][batch][N] canonical words and is never written.  `param` is the exponent of every row (monomial,
+ * d_exp == NULL) or g (automorphism).  d_exp is a device array of `batch` words, monomial only; row r of EVERY polynomial uses d_exp[r]
+ * (the polynomials of one GLWE ciphertext rotate together).  NTT_E_ARG: an unknown kind or flag bit; an even g or g >= 2N; d_exp != NULL
+ * with the automorphism; d_exp not 4-byte aligned; d_exp[0 .. batch) overlapping any written range; null or misaligned data pointers;
+ * polys == 0; the 2^31 - 1 row limits of ntt_gadget_decompose.  batch == 0 is NTT_OK.  Asynchronous on `stream`, no allocation, no host
+ * synchronisation: the exponents are read on the device.
+ *
+ * ntt_negacyclic_map: d_out is [polys][batch][N].  Out of place only -- the gather reads the whole row --: any overlap of the two ranges
+ * is NTT_E_ARG.  ONE launch; like ntt_gadget_decompose it needs no twiddles.
+ *
+ * ntt_gadget_decompose_map: d_digits is, bit for bit, ntt_gadget_decompose of ntt_negacyclic_map's output, in ONE launch: each source
+ * word is gathered once and its `levels` digits are written with 128-bit non-temporal stores.
+ *
+ * ntt_polymul_gadget_map_pre: block j of d_out is, bit for bit, what ntt_polymul_gadget_pre writes for the mapped operand; with a
+ * non-null d_addend ([outs][batch][N] canonical words) d_addend[j] is added mod p.  It ALWAYS takes the decomposition-kernel route: one
+ * launch of the map kernel d_a -> d_work (the digits of the mapped words), then exactly ntt_polymul_matvec_pre on d_work, then, with an
+ * addend, one elementwise in-place launch on d_out.  ntt_plan_info 15 does not apply to it.  d_a, d_work, d_bhat and d_out are pairwise
+ * disjoint.  d_addend may be d_a itself (the CMUX / blind-rotation case, outs == polys) or any range disjoint from d_work and d_out; it is
+ * only read.  The remaining rules are those of ntt_polymul_gadget_pre.
+ * Derived, NOT measured with counters (P = polys, K = levels, J = outs, words per row): against ntt_negacyclic_map followed by
+ * ntt_polymul_gadget_pre where that call runs the decomposition kernel, the fused decomposition saves the mapped copy's write and
+ * re-read, 2 P N words, and one launch per call.  The accumulate is a launch of its own after the forward passes and costs 3 J N words
+ * (read d_out, read d_addend, write d_out); fusing it into the last forward pass is not done. */
+enum { NTT_MAP_MONOMIAL = 0, NTT_MAP_AUTOMORPHISM = 1 };
+enum { NTT_MAP_MINUS_IDENTITY = 1 };
+int ntt_negacyclic_map(ntt_plan_t plan, const void *d_in, void *d_out, size_t polys, size_t batch, int kind, uint32_t param,
+                       const uint32_t *d_exp, int flags, void *stream);
+int ntt_gadget_decompose_map(ntt_plan_t plan, const void *d_a, size_t polys, size_t batch, int kind, uint32_t param, const uint32_t *d_exp,
+                             int flags, int log_base, int levels, int low_bits, void *d_digits, void *stream);
+int ntt_polymul_gadget_map_pre(ntt_plan_t plan, const void *d_a, size_t polys, int kind, uint32_t param, const uint32_t *d_exp, int flags,
+                               int log_base, int levels, int low_bits, void *d_work, const void *d_bhat, size_t bhat_rows, size_t outs,
+                               const void *d_addend, void *d_out, size_t batch, void *stream);
+
 /* Precondition check (blocking, diagnostic): how many of the batch*N words are >= p.  The transforms
  * assume canonical residues, as the reference's vector_modadd / vector_modsub do (src/aie_core.cc:41-62);
  * a non-canonical word gives an unspecified (but memory-safe) result: no kernel reads or writes outside the caller's

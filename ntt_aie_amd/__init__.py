@@ -2,9 +2,10 @@
 behind a C-ABI (include/ntt_hip.h), driven by a thin Python host that keeps the
 reference's (input, root, output) buffer contract (hal-lab-u-tokyo/ntt-aie,
 src/test.cpp:115-190, src/aie2.py:320-337)."""
-from ._lib import (LAYOUT_AIE_BLOCK16, LAYOUT_NATURAL, LIB_PATH, NTTError)  # noqa: F401
+from ._lib import (LAYOUT_AIE_BLOCK16, LAYOUT_NATURAL, LIB_PATH, NTT_MAP_AUTOMORPHISM, NTT_MAP_MINUS_IDENTITY, NTT_MAP_MONOMIAL, NTTError)  # noqa: F401
 
-__all__ = ["NTTPlan", "MultiDevicePlan", "NTTError", "LAYOUT_NATURAL", "LAYOUT_AIE_BLOCK16", "GOLDILOCKS", "to_device",
+__all__ = ["NTTPlan", "MultiDevicePlan", "NTTError", "LAYOUT_NATURAL", "LAYOUT_AIE_BLOCK16", "NTT_MAP_MONOMIAL", "NTT_MAP_AUTOMORPHISM",
+           "NTT_MAP_MINUS_IDENTITY", "GOLDILOCKS", "to_device",
            "to_host", "lde_from_evals", "version"]
 
 

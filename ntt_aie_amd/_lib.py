@@ -28,6 +28,11 @@ NTT_E_NODEVICE = -8
 NTT_E_NOMEM = -9
 NTT_E_INTERNAL = -10
 
+# ntt_negacyclic_map and its fused forms: kind, flags
+NTT_MAP_MONOMIAL = 0
+NTT_MAP_AUTOMORPHISM = 1
+NTT_MAP_MINUS_IDENTITY = 1
+
 LAYOUT_NATURAL = 0
 LAYOUT_AIE_BLOCK16 = 1
 
@@ -40,6 +45,7 @@ EXPORTS = (
     "ntt_forward_profile", "ntt_inverse", "ntt_pointwise_mul", "ntt_polymul_negacyclic", "ntt_count_noncanonical", "ntt_forward_stages",
     "ntt_polymul_prepare", "ntt_polymul_negacyclic_pre", "ntt_polymul_dot_pre", "ntt_polymul_matvec_pre",
     "ntt_gadget_decompose", "ntt_polymul_gadget_pre",
+    "ntt_negacyclic_map", "ntt_gadget_decompose_map", "ntt_polymul_gadget_map_pre",
 )
 
 
@@ -111,6 +117,11 @@ def open_library(path: str, since_v3: bool = True) -> C.CDLL:
         L.ntt_gadget_decompose.argtypes = [vp, vp, sz, sz, C.c_int, C.c_int, C.c_int, vp, vp]
     if hasattr(L, "ntt_polymul_gadget_pre"):
         L.ntt_polymul_gadget_pre.argtypes = [vp, vp, sz, C.c_int, C.c_int, C.c_int, vp, vp, sz, sz, vp, sz, vp]
+    if hasattr(L, "ntt_negacyclic_map"):
+        u32 = C.c_uint32
+        L.ntt_negacyclic_map.argtypes = [vp, vp, vp, sz, sz, C.c_int, u32, vp, C.c_int, vp]
+        L.ntt_gadget_decompose_map.argtypes = [vp, vp, sz, sz, C.c_int, u32, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.ntt_polymul_gadget_map_pre.argtypes = [vp, vp, sz, C.c_int, u32, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, sz, sz, vp, vp, sz, vp]
     L.ntt_count_noncanonical.argtypes = [vp, vp, sz, C.POINTER(C.c_uint64)]
     L.ntt_forward_stages.argtypes = [vp, vp, vp, sz, C.c_int, vp]
     return L

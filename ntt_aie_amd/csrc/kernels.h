@@ -105,6 +105,14 @@ hipError_t launch_matvec_rows(const FieldParams &fp, const void *a, const void *
 // middle launch does not decompose.  Needs p alone, no table
 hipError_t launch_gadget_decompose(const FieldParams &fp, const void *a, void *digits, int n, size_t polys, size_t batch, int log_base, int levels, int low_bits,
                                    hipStream_t s);
+// the signed negacyclic map of every row (negacyclic_map.h): out[q][r][j] = +-a[q][r][src(j)], minus a[q][r][j] with minus_identity; kind 0 the
+// monomial X^e with e = d_exp[r] (a device array of batch words) or, d_exp null, q for every row; kind 1 the automorphism with q = g^-1 mod 2N.
+// levels == 0: out is [polys][batch][2^n] words; levels > 0: out is [polys][levels][batch][2^n], the gadget digits of the mapped words (what
+// launch_gadget_decompose writes for them), each source word gathered once.  a is read only and lies apart from out.  ONE launch; p alone
+hipError_t launch_negacyclic_map(const FieldParams &fp, const void *a, void *out, int n, size_t polys, size_t batch, int kind, uint32_t q, const uint32_t *d_exp,
+                                 int minus_identity, int log_base, int levels, int low_bits, hipStream_t s);
+// in place: out[i] = out[i] + addend[i] mod p, canonical words, i < count -- the accumulate of ntt_polymul_gadget_map_pre
+hipError_t launch_add_rows(const FieldParams &fp, void *out, const void *addend, size_t count, hipStream_t s);
 // device-side table generation (no host upload): T[i] = base^e_kind(i), table form
 hipError_t launch_gen_table(const FieldParams &fp, void *T, int logn, int kind, uint64_t base_m, uint64_t one_m, hipStream_t s);
 // coset vector of ntt_plan_set_coset: s[i] = shift^bitrev_logn(i mod 2^logn), table form, i < len (len = max(2^logn, 4));

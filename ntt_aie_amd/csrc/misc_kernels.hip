@@ -8,6 +8,7 @@
 
 #include "field.h"
 #include "kernels.h"
+#include "negacyclic_map.h"
 
 #ifndef NTT_PW_UNROLL
 #define NTT_PW_UNROLL 2
@@ -332,6 +333,47 @@ __global__ __launch_bounds__(256) void gadget_decompose_kernel(const W *a, W *di
         for (int k = 0; k < levels; ++k) digits[(size_t) k * block + i] = (W) gadget_digit(g, (uint64_t) a[i], k * log_base, k == levels - 1);
 }
 
+// The signed negacyclic maps X^e . a and a(X^g), optionally minus a itself, and (DIGITS) the balanced gadget digits of the mapped words
+// (ntt_negacyclic_map, ntt_gadget_decompose_map, the first launch of ntt_polymul_gadget_map_pre; negacyclic_map.h has the index rule and
+// the thread's loops, shared with the host program that runs them under the sanitizers).  gadget_decompose_kernel's launch shape:
+// blockIdx.y is the polynomial q; within its [batch][N] block one thread per 16-byte DESTINATION chunk, grid-stride.  Row r of every
+// polynomial takes exps[r] (a device array, loaded per chunk) or the one exponent / ginv of m.q.  The sources are gathered word by word:
+// for the monomial adjacent lanes still read adjacent words, for the automorphism the stride is ginv and a row is read again from
+// cache.  One 128-bit non-temporal store per chunk, or `levels` of them to the blocks (q * levels + k) of the digits.
+template <class W, bool DIGITS>
+__global__ __launch_bounds__(256) void negacyclic_map_kernel(const W *a, W *out, size_t block, MapArgs m) {
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    a += (size_t) blockIdx.y * block;
+    out += (size_t) blockIdx.y * (size_t) (DIGITS ? m.gp.levels : 1) * block;
+    negacyclic_map_thread<W, DIGITS>(a, out, block, m, (size_t) blockIdx.x * blockDim.x + threadIdx.x, (size_t) gridDim.x * blockDim.x,
+                                     [](W *dst, size_t c, const MapChunk<W> &x) {
+                                         u32x4 xx;
+                                         __builtin_memcpy(&xx, &x, 16);
+                                         __builtin_nontemporal_store(xx, reinterpret_cast<u32x4 *>(dst) + c);
+                                     });
+}
+
+// The accumulate of ntt_polymul_gadget_map_pre: out[i] = out[i] + addend[i] mod p in place, canonical words, one thread per 16-byte chunk,
+// grid-stride, chunked like row_scale_kernel; a count that is no multiple of V (N = 2 of 4-byte words, an odd row count) ends word by word.
+template <class W>
+__global__ __launch_bounds__(256) void add_rows_kernel(W *out, const W *addend, size_t count, W p) {
+    constexpr int V = 16 / sizeof(W);
+    using u32x4 = unsigned int __attribute__((ext_vector_type(4)));
+    const size_t chunks = count / V, stride = (size_t) gridDim.x * blockDim.x;
+    for (size_t c = (size_t) blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += stride) {
+        const u32x4 xx = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(out) + c);
+        const Vec<W, V> y = *(reinterpret_cast<const Vec<W, V> *>(addend) + c);
+        Vec<W, V> x;
+        __builtin_memcpy(&x, &xx, 16);
+#pragma unroll
+        for (int k = 0; k < V; ++k) x.v[k] = map_addmod<W>(x.v[k], y.v[k], p);
+        u32x4 zz;
+        __builtin_memcpy(&zz, &x, 16);
+        __builtin_nontemporal_store(zz, reinterpret_cast<u32x4 *>(out) + c);
+    }
+    for (size_t i = chunks * V + (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) out[i] = map_addmod<W>(out[i], addend[i], p);
+}
+
 // out[i] = T[i] * c, both in table (Montgomery) form: the scaled stage-0 twiddles of the inverse transform (pass.h: fold_scale)
 template <class F>
 __global__ __launch_bounds__(256) void scale_table_kernel(const typename F::W *T, typename F::W *out, size_t count,
@@ -455,6 +497,40 @@ hipError_t launch_gadget_decompose(const FieldParams &fp, const void *a, void *d
             if (err != hipSuccess) return err;
         }
         return hipSuccess;
+    };
+    return field_word_bytes(fp) == 4 ? go(uint32_t{}) : go(uint64_t{});
+}
+
+hipError_t launch_negacyclic_map(const FieldParams &fp, const void *a, void *out, int n, size_t polys, size_t batch, int kind, uint32_t q, const uint32_t *d_exp,
+                                 int minus_identity, int log_base, int levels, int low_bits, hipStream_t s) {
+    const size_t block = batch << n;
+    if (block == 0 || polys == 0) return hipSuccess;
+    if (levels != 0 && !gadget_params_ok(fp.p, log_base, levels, low_bits)) return hipErrorInvalidValue;
+    const MapArgs m{kind, n, q, d_exp, minus_identity, fp.p, GadgetParams{log_base, levels, low_bits}};
+    auto go = [&](auto w) {
+        using W = decltype(w);
+        // blockIdx.y is the polynomial: one launch up to 65535 polynomials, a slice per 65535 beyond
+        for (size_t y = 0; y < polys; y += 65535u) {
+            const size_t ny = polys - y < 65535u ? polys - y : 65535u;
+            const dim3 grid(grid_for((block + 16 / sizeof(W) - 1) / (16 / sizeof(W))), (unsigned) ny);
+            if (levels != 0)
+                hipLaunchKernelGGL((negacyclic_map_kernel<W, true>), grid, dim3(256), 0, s, (const W *) a + y * block, (W *) out + y * (size_t) levels * block, block, m);
+            else
+                hipLaunchKernelGGL((negacyclic_map_kernel<W, false>), grid, dim3(256), 0, s, (const W *) a + y * block, (W *) out + y * block, block, m);
+            const hipError_t err = hipGetLastError();
+            if (err != hipSuccess) return err;
+        }
+        return hipSuccess;
+    };
+    return field_word_bytes(fp) == 4 ? go(uint32_t{}) : go(uint64_t{});
+}
+
+hipError_t launch_add_rows(const FieldParams &fp, void *out, const void *addend, size_t count, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    auto go = [&](auto w) {
+        using W = decltype(w);
+        hipLaunchKernelGGL(add_rows_kernel<W>, dim3(grid_for((count + 16 / sizeof(W) - 1) / (16 / sizeof(W)))), dim3(256), 0, s, (W *) out, (const W *) addend, count, (W) fp.p);
+        return hipGetLastError();
     };
     return field_word_bytes(fp) == 4 ? go(uint32_t{}) : go(uint64_t{});
 }

@@ -15,6 +15,7 @@
 #include "../../include/ntt_hip.h"
 #include "guard.h"
 #include "kernels.h"
+#include "negacyclic_map.h"
 #include "plan.h"
 #include "sequence.h"
 
@@ -155,6 +156,26 @@ int check_layout(const ntt_plan *pl, int layout) {
     return NTT_OK;
 }
 
+// the map arguments the three *_map entry points share (batch > 0): NTT_OK and *q = the word the kernel takes (the exponent of every
+// row, or g^-1 mod 2N), or NTT_E_ARG
+int check_map(const ntt_plan *pl, int kind, uint32_t param, const uint32_t *d_exp, int flags, uint32_t *q) {
+    if (kind != NTT_MAP_MONOMIAL && kind != NTT_MAP_AUTOMORPHISM) return NTT_E_ARG;
+    if (flags & ~NTT_MAP_MINUS_IDENTITY) return NTT_E_ARG;
+    if ((uintptr_t) d_exp & 3u) return NTT_E_ARG;
+    *q = param;
+    if (kind == NTT_MAP_AUTOMORPHISM) {
+        if (d_exp || !(param & 1u) || param >= (2u << pl->logn)) return NTT_E_ARG;
+        *q = ntt::map_ginv(param, pl->logn);
+    }
+    return NTT_OK;
+}
+using u128 = unsigned __int128;
+// d_exp[0 .. batch) against a written range [lo, hi)
+bool exps_overlap(const uint32_t *d_exp, size_t batch, u128 lo, u128 hi) {
+    const u128 e0 = (uintptr_t) d_exp, e1 = e0 + (u128) batch * 4;
+    return d_exp && e0 < hi && lo < e1;
+}
+
 // One step of a sequence (sequence.h) to its launcher, inside the ROCTX range of that pass
 int launch_step(const char *what, const ntt::Step &st, hipStream_t s) {
     RoctxRange pass(what, st.contig, st.args.s0 - st.args.mat_w, st.log_m);
@@ -268,6 +289,17 @@ int ntt_plan_set_debug(ntt_plan_t pl, int flags) NTT_GUARD {
     if (!pl) return NTT_E_ARG;
     pl->dbg = flags;
     return NTT_OK;
+} NTT_GUARD_END
+
+// libntt_hip_exp.so only, never declared in include/ntt_hip.h: the accumulate launch of ntt_polymul_gadget_map_pre alone,
+// d_out[i] = d_out[i] + d_addend[i] mod p over rows * N canonical words (tools/bench_negacyclic_map.py: the leg that maps and multiplies
+// in separate calls adds through the same kernel as the fused call)
+int ntt_add_rows_exp(ntt_plan_t pl, void *d_out, const void *d_addend, size_t rows, void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_out, d_addend, rows);
+    if (rc || rows == 0) return rc;
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    return (int) ntt::launch_add_rows(pl->field, d_out, d_addend, rows << pl->logn, (hipStream_t) stream);
 } NTT_GUARD_END
 #endif
 
@@ -1023,6 +1055,107 @@ int ntt_polymul_gadget_pre(ntt_plan_t pl, const void *d_a, size_t polys, int log
             RoctxRange dec("product(gadget): decomposition");
             return (int) ntt::launch_gadget_decompose(pl->field, src, digits, pl->logn, polys, batch, log_base, levels, low_bits, s);
         });
+} NTT_GUARD_END
+
+int ntt_negacyclic_map(ntt_plan_t pl, const void *d_in, void *d_out, size_t polys, size_t batch, int kind, uint32_t param, const uint32_t *d_exp, int flags,
+                       void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_in, d_out, batch);
+    if (rc) return rc;
+    if (batch == 0) return NTT_OK;
+    uint32_t q;
+    if ((rc = check_map(pl, kind, param, d_exp, flags, &q))) return rc;
+    if (polys == 0 || polys > 0x7FFFFFFFull / batch) return NTT_E_ARG;
+    {
+        const u128 row = table_bytes(pl), top = (u128) 1 << 63;
+        const u128 a0 = (uintptr_t) d_in, a1 = a0 + (u128) polys * batch * row, o0 = (uintptr_t) d_out, o1 = o0 + (u128) polys * batch * row;
+        // out of place only: the gather reads the whole row
+        if (a1 > top || o1 > top || (a0 < o1 && o0 < a1) || exps_overlap(d_exp, batch, o0, o1)) return NTT_E_ARG;
+    }
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    RoctxRange whole("ntt_negacyclic_map");
+    return (int) ntt::launch_negacyclic_map(pl->field, d_in, d_out, pl->logn, polys, batch, kind, q, d_exp, flags & NTT_MAP_MINUS_IDENTITY, 0, 0, 0, (hipStream_t) stream);
+} NTT_GUARD_END
+
+int ntt_gadget_decompose_map(ntt_plan_t pl, const void *d_a, size_t polys, size_t batch, int kind, uint32_t param, const uint32_t *d_exp, int flags, int log_base,
+                             int levels, int low_bits, void *d_digits, void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_a, d_digits, batch);
+    if (rc) return rc;
+    if (batch == 0) return NTT_OK;
+    uint32_t q;
+    if ((rc = check_map(pl, kind, param, d_exp, flags, &q))) return rc;
+    if (!ntt::gadget_params_ok(pl->p, log_base, levels, low_bits)) return NTT_E_ARG;
+    if (polys == 0 || polys > 0x7FFFFFFFull / batch / (size_t) levels) return NTT_E_ARG;  // the digits are polys * levels * batch rows of a product
+    {
+        const u128 row = table_bytes(pl), top = (u128) 1 << 63;
+        const u128 a0 = (uintptr_t) d_a, a1 = a0 + (u128) polys * batch * row, g0 = (uintptr_t) d_digits, g1 = g0 + (u128) polys * (u128) levels * batch * row;
+        if (a1 > top || g1 > top || (a0 < g1 && g0 < a1) || exps_overlap(d_exp, batch, g0, g1)) return NTT_E_ARG;
+    }
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    RoctxRange whole("ntt_gadget_decompose_map");
+    return (int) ntt::launch_negacyclic_map(pl->field, d_a, d_digits, pl->logn, polys, batch, kind, q, d_exp, flags & NTT_MAP_MINUS_IDENTITY, log_base, levels, low_bits,
+                                            (hipStream_t) stream);
+} NTT_GUARD_END
+
+int ntt_polymul_gadget_map_pre(ntt_plan_t pl, const void *d_a, size_t polys, int kind, uint32_t param, const uint32_t *d_exp, int flags, int log_base, int levels,
+                               int low_bits, void *d_work, const void *d_bhat, size_t bhat_rows, size_t outs, const void *d_addend, void *d_out, size_t batch,
+                               void *stream) NTT_GUARD {
+    int rc = check_io(pl, d_a, d_bhat, batch);
+    if (rc) return rc;
+    if (batch && (!d_out || ((uintptr_t) d_out & 15u) || !d_work || ((uintptr_t) d_work & 15u) || ((uintptr_t) d_addend & 15u))) return NTT_E_ARG;
+    if (batch && bhat_rows != 1 && bhat_rows != batch) return NTT_E_ARG;
+    uint32_t q = 0;
+    if (batch && (rc = check_map(pl, kind, param, d_exp, flags, &q))) return rc;
+    if (batch && !ntt::gadget_params_ok(pl->p, log_base, levels, low_bits)) return NTT_E_ARG;
+    if (batch && (polys == 0 || polys > 0x7FFFFFFFull / batch / (size_t) levels)) return NTT_E_ARG;  // terms * batch rows, terms = polys * levels
+    if (batch && (outs == 0 || outs > 0x7FFFFFFFull / batch)) return NTT_E_ARG;                      // the forward passes over outs * batch rows
+    if (!pl->has_table) return NTT_E_NOTABLE;
+    if (!pl->has_inv) return NTT_E_NOTINVERTIBLE;
+    if (batch == 0) return NTT_OK;
+    const size_t terms = polys * (size_t) levels;
+    {
+        const u128 row = table_bytes(pl), top = (u128) 1 << 63;  // no buffer ends beyond that: ranges that cannot wrap
+        const u128 lo[4] = {(uintptr_t) d_a, (uintptr_t) d_work, (uintptr_t) d_bhat, (uintptr_t) d_out};
+        const u128 hi[4] = {lo[0] + (u128) polys * batch * row, lo[1] + (u128) terms * batch * row, lo[2] + (u128) outs * terms * bhat_rows * row,
+                            lo[3] + (u128) outs * batch * row};
+        for (int i = 0; i < 4; ++i) {
+            if (hi[i] > top) return NTT_E_ARG;
+            for (int j = 0; j < i; ++j)
+                if (lo[i] < hi[j] && lo[j] < hi[i]) return NTT_E_ARG;  // pairwise disjoint
+        }
+        // what is only read -- the exponents and the addend -- lies apart from the two written ranges; the addend may be a itself (CMUX)
+        if (exps_overlap(d_exp, batch, lo[1], hi[1]) || exps_overlap(d_exp, batch, lo[3], hi[3])) return NTT_E_ARG;
+        if (d_addend) {
+            const u128 d0 = (uintptr_t) d_addend, d1 = d0 + (u128) outs * batch * row;
+            if (d1 > top || (d0 < hi[1] && lo[1] < d1) || (d0 < hi[3] && lo[3] < d1)) return NTT_E_ARG;
+        }
+    }
+    DeviceGuard g(pl->device);
+    if (g.err != hipSuccess) return (int) g.err;
+    hipStream_t s = (hipStream_t) stream;
+    RoctxRange whole("ntt_polymul_gadget_map_pre");
+    const std::vector<PassDesc> &passes = passes_for(pl, batch);  // by batch, as ntt_polymul_matvec_pre selects it
+    {
+        RoctxRange dec("product(gadget map): map and decomposition");
+        rc = (int) ntt::launch_negacyclic_map(pl->field, d_a, d_work, pl->logn, polys, batch, kind, q, d_exp, flags & NTT_MAP_MINUS_IDENTITY, log_base, levels, low_bits, s);
+        if (rc) return rc;
+    }
+    rc = ntt::seq_polymul_matvec(
+        *pl, passes, d_work, d_bhat, bhat_rows, terms, outs, d_out, batch,
+        [&](const ntt::Step &st) {
+            return launch_step(st.family == ntt::STEP_PRODUCT ? (st.args.mv_outs ? "product(gadget map): fused middle, two outputs" : "product(gadget map): fused middle")
+                               : st.inverse                   ? "product(gadget map): inv pass"
+                                                              : "product(gadget map): fwd pass",
+                               st, s);
+        },
+        [&](void *buf, const void *hat, void *out) {
+            RoctxRange sum("product(gadget map): row sums");
+            return (int) ntt::launch_matvec_rows(pl->field, buf, hat, out, pl->logn, batch, bhat_rows, terms, outs, ntt::pw_scale_form(*pl, pl->ninv_plain), s);
+        });
+    if (rc || !d_addend) return rc;
+    RoctxRange add("product(gadget map): accumulate");
+    return (int) ntt::launch_add_rows(pl->field, d_out, d_addend, (outs * batch) << pl->logn, s);
 } NTT_GUARD_END
 
 int ntt_count_noncanonical(ntt_plan_t pl, const void *d_buf, size_t batch, uint64_t *host_count) NTT_GUARD {

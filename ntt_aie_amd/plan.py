@@ -559,6 +559,92 @@ class NTTPlan:
                                                 out.data_ptr(), rows_a, self._stream(stream)), "ntt_polymul_gadget_pre")
         return out
 
+    def _map_args(self, a: torch.Tensor, kind: int, param: int, exps: torch.Tensor | None, minus_identity: bool) -> tuple[int, int, int, int, int]:
+        """(polys, batch, param word, exps pointer or None, flags) of the three *_map calls; the library checks kind, g and the flag"""
+        if a.dim() != 3 or a.shape[2] != self.n:
+            raise ValueError("a must be [polys, batch, N]")
+        polys, rows = int(a.shape[0]), int(a.shape[1])
+        if polys == 0:
+            raise ValueError("a has no polynomials")
+        ptr = None
+        if exps is not None:
+            if not exps.is_cuda or exps.device.index != self.device:
+                raise ValueError("exps is not on cuda:%d" % self.device)
+            if exps.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not exps.is_contiguous() or exps.numel() != rows:
+                raise ValueError("exps must be a contiguous uint32 / int32 tensor of batch elements")
+            ptr = exps.data_ptr()
+        return polys, rows, int(param) & 0xFFFFFFFF, ptr, _lib.NTT_MAP_MINUS_IDENTITY if minus_identity else 0
+
+    def negacyclic_map(self, a: torch.Tensor, kind: int, param: int = 0, exps: torch.Tensor | None = None, minus_identity: bool = False,
+                       out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """The signed coefficient permutation of every row of a (ntt_negacyclic_map; include/ntt_hip.h has the definition): kind
+        NTT_MAP_MONOMIAL gives X^e * a mod (x^N + 1) with e = exps[r] for row r of every polynomial (a device tensor of batch words, read on
+        the device) or, without exps, e = param for every row -- any integer, taken mod 2N --; kind NTT_MAP_AUTOMORPHISM gives a(X^g) with
+        g = param odd and below 2N.  minus_identity subtracts a itself.  a is [polys, batch, N] canonical words and is only read; `out`, of
+        the same shape, must not overlap it.  Needs no table."""
+        polys, rows, word, ptr, flags = self._map_args(a, kind, param, exps, minus_identity)
+        if out is None:
+            out = self._out_like(a, stream)
+        if tuple(out.shape) != tuple(a.shape):
+            raise ValueError("out must be [polys, batch, N]")
+        self._operand(a)
+        self._operand(out)
+        check(_lib.lib().ntt_negacyclic_map(self._h, a.data_ptr(), out.data_ptr(), polys, rows, kind, word, ptr, flags, self._stream(stream)), "ntt_negacyclic_map")
+        return out
+
+    def gadget_decompose_map(self, a: torch.Tensor, kind: int, param: int = 0, exps: torch.Tensor | None = None, minus_identity: bool = False, *,
+                             log_base: int, levels: int, low_bits: int = 0, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """gadget_decompose(negacyclic_map(a, ...)), bit for bit, in one launch (ntt_gadget_decompose_map): [polys, levels, batch, N]."""
+        polys, rows, word, ptr, flags = self._map_args(a, kind, param, exps, minus_identity)
+        if levels < 1:
+            raise ValueError("levels must be at least 1")
+        if out is None:
+            out = torch.empty((polys, levels, rows, self.n), dtype=a.dtype, device=a.device)
+        if tuple(out.shape) != (polys, levels, rows, self.n):
+            raise ValueError("out must be [polys, levels, batch, N]")
+        self._operand(a)
+        self._operand(out)
+        check(_lib.lib().ntt_gadget_decompose_map(self._h, a.data_ptr(), polys, rows, kind, word, ptr, flags, log_base, levels, low_bits, out.data_ptr(),
+                                                  self._stream(stream)), "ntt_gadget_decompose_map")
+        return out
+
+    def polymul_gadget_map_pre(self, a: torch.Tensor, kind: int, param: int = 0, exps: torch.Tensor | None = None, minus_identity: bool = False, *,
+                               log_base: int, levels: int, low_bits: int, bhat: torch.Tensor, addend: torch.Tensor | None = None,
+                               work: torch.Tensor | None = None, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """polymul_gadget_pre(negacyclic_map(a, ...), ...) + addend, bit for bit (ntt_polymul_gadget_map_pre): the map and the digits in one
+        launch a -> work, the matrix-vector product of work, and with `addend`, [J, batch, N] canonical words, out[j] += addend[j] mod p.
+        addend may be a itself (J == polys: the blind-rotation step) or any buffer apart from work and out.  The other arguments are
+        polymul_gadget_pre's; a is NOT written."""
+        polys, rows_a, word, ptr, flags = self._map_args(a, kind, param, exps, minus_identity)
+        if levels < 1:
+            raise ValueError("levels must be at least 1")
+        terms = polys * levels
+        if bhat.dim() == 4 and tuple(bhat.shape[1:]) == (terms, rows_a, self.n):
+            rows = rows_a
+        elif (bhat.dim() == 3 and tuple(bhat.shape[1:]) == (terms, self.n)) or (bhat.dim() == 4 and tuple(bhat.shape[1:]) == (terms, 1, self.n)):
+            rows = 1
+        else:
+            raise ValueError("bhat must be [outs, polys * levels, batch, N], or [outs, polys * levels, N] / [outs, polys * levels, 1, N] (broadcast)")
+        outs = int(bhat.shape[0])
+        if outs == 0:
+            raise ValueError("bhat has no outputs")
+        if work is None:
+            work = torch.empty((terms, rows_a, self.n), dtype=a.dtype, device=a.device)
+        if work.numel() != terms * rows_a * self.n:
+            raise ValueError("work must hold polys * levels * batch * N words")
+        if out is None:
+            out = torch.empty((outs, rows_a, self.n), dtype=a.dtype, device=a.device)
+        if out.dim() != 3 or tuple(out.shape) != (outs, rows_a, self.n):
+            raise ValueError("out must be [outs, batch, N]")
+        if addend is not None and tuple(addend.shape) != (outs, rows_a, self.n):
+            raise ValueError("addend must be [outs, batch, N]")
+        for t in (a, work, bhat, out) + (() if addend is None else (addend,)):
+            self._operand(t)
+        check(_lib.lib().ntt_polymul_gadget_map_pre(self._h, a.data_ptr(), polys, kind, word, ptr, flags, log_base, levels, low_bits, work.data_ptr(), bhat.data_ptr(),
+                                                    rows, outs, None if addend is None else addend.data_ptr(), out.data_ptr(), rows_a, self._stream(stream)),
+              "ntt_polymul_gadget_map_pre")
+        return out
+
     def count_noncanonical(self, buf: torch.Tensor) -> int:
         """How many words of `buf` are >= p (the transforms require canonical residues)."""
         b = self._batch(buf)
